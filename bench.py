@@ -6,8 +6,11 @@ on-device, seeded per rank): backbone (train-mode BN) -> LSTM(128) -> FC head ->
 BCELoss -> backward (gradient all-reduce over RCCL overlapped with it) ->
 clip_grad_norm_(1.0) -> Adam(lr 1e-5, wd 1e-4) (train_visual.py:533-577 semantics).
 The headline is the unfrozen backbone (train_visual.py:551-556, every epoch after the
-3rd); the frozen backbone (as shipped, XceptionLSTMV.py:15-16) is measured in the same
-run and reported under "frozen".
+3rd).  A plain run sets up, warms up, times ``--steps`` steps of it and prints the line
+(``ms_per_step``: one timed step); ``--dump-outputs DIR`` also writes what the last timed step
+computed (dump_outputs).  ``--full`` adds every secondary measurement to the same run and line:
+the frozen backbone (as shipped, XceptionLSTMV.py:15-16) under "frozen", the per-kernel roofline
+region, the diagnostics, the b = 4 line, the measured peaks and the CPU baseline.
 
 Other configurations (secondary lines, BASELINE.json configs):
   --model xception : C2, Xception(num_classes=1) trained per frame, 64 frames of 299^2
@@ -19,8 +22,8 @@ Other configurations (secondary lines, BASELINE.json configs):
                      64^2, autocast + GradScaler, accumulation 4, AdamW, OneCycleLR, averaged
                      model; a step is one micro-batch (the optimizer steps on every 4th)
 
-Launch: ``python bench.py [--gpus N --steps K --warmup W]``.  Under torch.distributed.run
-(WORLD_SIZE set) one process drives one GPU; with --gpus N > 1 and no WORLD_SIZE this
+Launch: ``python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]``.
+Under torch.distributed.run (WORLD_SIZE set) one process drives one GPU; with --gpus N > 1 and no WORLD_SIZE this
 process starts N ranks itself through torch.distributed.run (before touching the GPU) and
 exits with their status.  Rank 0 prints ONE JSON line.
 """
@@ -53,11 +56,19 @@ def parse():
     ap.add_argument("--frames", type=int, default=None, help="frames per clip (default 16; 120 for lstma)")
     ap.add_argument("--size", type=int, default=299)
     ap.add_argument("--mode", choices=["unfrozen", "frozen", "both"], default=None,
-                    help="backbone training (lstmv default: both, unfrozen is the headline; lstma: frozen)")
+                    help="backbone training (lstmv default: unfrozen, the headline; both with --full; lstma: frozen)")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
-    ap.add_argument("--cpu-baseline", choices=["on", "off"], default="on")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline region also run every secondary measurement (the frozen backbone, the "
+                         "per-kernel roofline region, --diag, --small-batch, --measured-peaks, --cpu-baseline); "
+                         "without it each of them is off unless its own option asks for it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step of the headline mode computed (loss, "
+                         "model output, clip features, gradients, updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", choices=["on", "off"], default=None, help="default: on with --full")
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true",
+                    help="with --full: leave out the second timed region with HIP events around the roofline kernels")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the whole train step as one HIP graph (on: world size 1; auto = on for lstma only, "
                          "measured slower on the others)")
@@ -67,20 +78,28 @@ def parse():
                          "(xcp.ddp proxy mode, profiles/r06_ddp_proxy.txt); 0 = off")
     ap.add_argument("--ddp-proxy-busbw", type=float, default=300.0, help="stand-in all-reduce bus bandwidth, GB/s")
     ap.add_argument("--ddp-proxy-blocks", type=int, default=32, help="stand-in workgroups (RCCL channel blocks)")
-    ap.add_argument("--small-batch", type=int, default=4,
+    ap.add_argument("--small-batch", type=int, default=None,
                     help="lstmv: also time the unfrozen step at this many clips/GPU (train_visual.py:545 uses 4; "
-                         "0: off)")
-    ap.add_argument("--measured-peaks", choices=["on", "off"], default="on",
+                         "0: off; default: 4 with --full)")
+    ap.add_argument("--measured-peaks", choices=["on", "off"], default=None,
                     help="time a bf16 GEMM (torch.matmul -> hipBLASLt, 8192^3) and a device copy after the timed "
-                         "region and report the roofline fractions against them too")
-    ap.add_argument("--diag", choices=["on", "off"], default="on",
+                         "region and report the roofline fractions against them too (default: on with --full)")
+    ap.add_argument("--diag", choices=["on", "off"], default=None,
                     help="per-step / forward / backward device times, allocator counters over the timed region, "
                          "the MFMA-load clock before and after it, and (lstmv) the unfrozen step with the weight "
-                         "gradients on the main stream")
+                         "gradients on the main stream (default: on with --full)")
     ap.add_argument("--optim", choices=["fused", "torch"], default="fused",
                     help="fused: xcp.optim.FusedAdamClip (clip + Adam in two HIP launches); torch: "
                          "clip_grad_norm_ + torch.optim.Adam(fused=True)")
     a = ap.parse_args()
+    # a plain run does what the headline figure needs; --full turns the secondary measurements on
+    extras = "on" if a.full else "off"
+    a.cpu_baseline = a.cpu_baseline or extras
+    a.measured_peaks = a.measured_peaks or extras
+    a.diag = a.diag or extras
+    a.kernel_timing = a.full and not a.no_kernel_timing
+    if a.small_batch is None:
+        a.small_batch = 4 if a.full else 0
     audio = a.model == "lstma"
     if a.model == "auface":
         a.frames = a.frames or 75
@@ -95,7 +114,7 @@ def parse():
         a.steps = max(acc, -(-a.steps // acc) * acc)
     a.frames = a.frames or (120 if audio else 16)
     a.batch = a.batch or (64 if a.model == "xception" else 16)
-    a.mode = a.mode or ("frozen" if audio else "unfrozen" if a.model == "xception" else "both")
+    a.mode = a.mode or ("frozen" if audio else "both" if a.model == "lstmv" and a.full else "unfrozen")
     if audio:
         a.size = 64
     return a
@@ -326,6 +345,8 @@ class Run:
         torch.manual_seed(0)
         B, T, S = args.batch, args.frames, args.size
         self.dev = dev
+        self.keep = bool(args.dump_outputs)   # hold the step's outputs for dump_outputs()
+        self.last = {}
         if args.model == "auface":
             from Models.AUFaceModel import AUFaceCrossDetector
             from xcp.auface import AUFaceTrainer
@@ -416,17 +437,25 @@ class Run:
         if self.args.model == "auface":
             loss, _, _ = self.trainer.micro_step(self.i, 1 << 30, self.batch)
             self.i += 1
+            if self.keep:
+                self.last = {"loss": loss.detach()}
             if ev is not None:
                 for e in ev[1:]:
                     e.record()
             return loss
         self.buckets.zero()
         ddp.broadcast_buffers(self.model)
+        feats = None
         if self.args.model == "xception":
             out = self.model(self.x)
         else:
-            out = self.model(self.model.extract_features(self.x, self.dev))
+            feats = self.model.extract_features(self.x, self.dev)
+            out = self.model(feats)
         loss = self.crit(out, self.y)
+        if self.keep:
+            self.last = {"output": out.detach(), "loss": loss.detach()}
+            if feats is not None:
+                self.last["features"] = feats.detach()
         if ev is not None:
             ev[1].record()
         loss.backward()
@@ -439,6 +468,33 @@ class Run:
         if ev is not None:
             ev[3].record()
         return loss
+
+
+DUMP_SAMPLE = 1 << 21   # elements kept of the flattened gradients / parameters (8 MB each as float32)
+
+
+def dump_outputs(run, path):
+    """Write what the last step of ``run`` left for its caller as ``path/<name>.npy`` (float32; float64
+    for the per-parameter norms): the loss, the model output, the clip features, and of the gradients
+    and the updated parameters (flattened in parameter order) the same DUMP_SAMPLE seeded positions
+    plus every tensor's L2 norm.  Inputs and initial weights are seeded, so two builds run with the
+    same arguments write arrays that compare position for position."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.float().cpu().numpy() for k, v in run.last.items()}
+    params = [p for p in run.model.parameters() if p.requires_grad]
+    for name, tensors in (("params", [p.detach() for p in params]),
+                          ("grads", [torch.zeros_like(p) if p.grad is None else p.grad.detach() for p in params])):
+        flat = torch.cat([t.float().reshape(-1) for t in tensors]).cpu()
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(2024))
+            flat = flat[idx.sort().values]
+        arrays[name + "_sample"] = flat.numpy()
+        arrays[name + "_norms"] = np.array([t.double().norm().item() for t in tensors], dtype=np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
 
 
 def measured_peaks(dev):
@@ -598,7 +654,7 @@ def main():
             log(f"{args.model} {mode}: building model")
         run = Run(args, mode, dev, rank, world)
         timer = None
-        if not args.no_kernel_timing and mode == modes[0] and not audio and not fusion:
+        if args.kernel_timing and mode == modes[0] and not audio and not fusion:
             hm = middle_hw(S)
             cp = engine.pc(728)   # the 728-channel flow's channel pitch (736: padded rows)
             timer = ops.KernelTimer({"pw_gemm_728": lambda name, a: name == "gemm_nt" and a["M"] == frames * hm * hm
@@ -633,6 +689,8 @@ def main():
             torch.cuda.current_stream().wait_stream(hs)
         else:
             elapsed, loss = timed(run, steps, args.warmup, world, None, dg)
+        if args.dump_outputs and mode == modes[0] and rank == 0:
+            dump_outputs(run, args.dump_outputs)
         if mode == modes[0] and getattr(getattr(run, "buckets", None), "proxy", None) is not None:
             from xcp import ddp as _ddp
             proxy_rep = _ddp.proxy_report(run.buckets, steps)
