@@ -150,8 +150,24 @@ XCP_DEV void stage(const T* __restrict__ src, char* dst, const TileGeo& g, long 
   }
 }
 
+// Logical work-item id of this workgroup.  xcd_remap gives each XCD one contiguous eighth of the ids, so
+// the grid works on eight places an eighth of the tensor apart at any time.  When the frame count is a
+// multiple of 8 the frames are dealt round-robin to the XCDs instead (workgroup b runs on XCD b % 8; a
+// frame's `per` workgroups stay on one XCD, so the 128-B lines that neighbouring channel slices share
+// are still fetched into one L2): the grid then passes over the tensor once, first frame to last, in
+// time, as the pointwise GEMMs before and after it do.  A bijection on [0, gridDim.x) either way, and
+// every item computes what it did, so the outputs are bitwise the same.  In the train step the 19^2 x 736
+// launches run 68.7 -> 63.1 us and the pointwise GEMM after them 138 -> 133 us; the step +0.9 ... +1.3 %
+// (profiles/r07_walk_step_ab.txt, r07_v0 / r07_v1_kernels.txt).
+XCP_DEV int fwd_item_id(int per) {
+  const int nfr = gridDim.x / per;   // (gridDim.x = frames * per)
+  if (nfr % 8 != 0) return xcd_remap(blockIdx.x, gridDim.x);
+  const int xcd = blockIdx.x % 8, j = blockIdx.x / 8;   // j < (nfr / 8) * per
+  return ((j / per) * 8 + xcd) * per + j % per;
+}
+
 XCP_DEV int block_coords(int ngroups, const TileGeo& g, int& grp, int& n, int& th0, int& tw0) {
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int id = fwd_item_id(ngroups * g.nth * g.ntw);
   grp = id % ngroups;
   const int sp = id / ngroups;
   const int ntiles = g.nth * g.ntw;
@@ -432,6 +448,8 @@ XCP_DEV RowMap row_map(int N, int ncg, int ngroups, int nbands = 1, bool xcd = f
   // xcd: the workgroups holding consecutive channel slices of a pixel row run on one XCD, so the
   // 128-B lines two of them share (every odd pixel of a 1,472-B row starts mid-line) are fetched
   // into one L2 instead of two
+  // (dealing the workgroups round-robin to the XCDs in chunks of `ngroups`, as the forward's fwd_item_id
+  // does with frames, measured 0.35 % slower in the step: profiles/r07_walk_step_ab.txt)
   const int wg = xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
   const int gw = __builtin_amdgcn_readfirstlane(wg * 4 + (threadIdx.x >> 6));
   m.live = gw < N * ncg * nbands * ngroups;

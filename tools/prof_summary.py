@@ -187,7 +187,7 @@ def contention(path):
               f"last end (bench.py's live figure: HIP events around the op)")
 
 
-TN_KERNELS = ("gemm_tn256_kernel", "gemm_tn_kernel")
+TN_KERNELS = ("gemm_tn256q_kernel", "gemm_tn256_kernel", "gemm_tn_kernel")
 PEAK_BF16_TF = 2500.0
 
 
