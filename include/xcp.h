@@ -289,6 +289,30 @@ int xcp_lstm_fwd(const float* xproj, const float* whh, const float* whhT, const 
 int xcp_lstm_bwd(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
                  const float* gates, float* dgates, float* work, int B, int T, int H, int kernel, xcp_stream_t stream);
 
+/* ---- LSTM recurrence over zero-padded clips of unequal length (lstm_varlen.hip) ----
+ * The arguments of xcp_lstm_fwd / xcp_lstm_bwd plus lens [B] (int, device memory; clamped to [0, T]
+ * by the kernels, never read by the host, so a call is capturable in a HIP graph).  Semantics of
+ * pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length = T): for L = lens[b],
+ * out[b][t >= L] = 0, hn / cn are the state after step L - 1 (0 for L = 0); the backward ignores
+ * dout[b][t >= L], takes dhn / dcn in at step L - 1 and writes dgates[b][t >= L] = 0.  With every
+ * lens[b] = T the results are bit-identical to the fixed-length entry points on the same kernel family.
+ * Saved state past a clip's end: hprev rows are zero (they meet zero dgates rows in the weight
+ * gradient and must be finite); cst and gates rows are left unwritten and never used.
+ * Kernel by shape: H = 64 / 128 register-resident, one workgroup per clip that leaves when its clip
+ * ends; H = 256 / 512 / 1024 with B <= 32 the per-step kernels, cell threads masked per clip (never
+ * the persistent, gather or clip-grouped kernels, whatever XCP_LSTM_PERSIST / XCP_LSTM_BWD say); any
+ * other shape, and kernel = 1, the generic pair, which reads whhT: xcp_lstm_varlen_needs_whhT(B, H,
+ * kernel) returns 1 then.  out, hprev and dgates must be 16-byte aligned.
+ * xcp_lstm_bwd_varlen's work: B*H + 4*H*H floats (the per-step kernels' cell-gradient carry and a
+ * transposed W_hh; may be null where the per-step kernels are not taken). */
+int xcp_lstm_varlen_needs_whhT(int B, int H, int kernel);
+int xcp_lstm_fwd_varlen(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh,
+                        float* out, float* hprev, float* cst, float* gates, float* hn, float* cn, const int* lens, int B,
+                        int T, int H, int kernel, xcp_stream_t stream);
+int xcp_lstm_bwd_varlen(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
+                        const float* gates, float* dgates, float* work, const int* lens, int B, int T, int H, int kernel,
+                        xcp_stream_t stream);
+
 /* ---- diagnostic (bench.py only; no reference counterpart) ----
  * blocks workgroups (one per CU) each run `iters` x 4 back-to-back bf16 MFMAs; out: DEVICE int64
  * [2 * blocks + 256]: out[2b] = shader cycles of block b's loop, out[2b + 1] = 100 MHz real-time

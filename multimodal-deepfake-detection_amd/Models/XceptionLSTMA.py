@@ -39,8 +39,15 @@ class XceptionLSTMA(nn.Module):
         frame_features = self.feature_extractor(frames)
         return frame_features.view(batch_size, time_steps, frame_features.shape[-1])
 
-    def forward(self, features):
-        lstm_out, _ = self.lstm(features)
-        lstm_out = lstm_out[:, -1, :]
+    def forward(self, features, seq_lengths=None):
+        """``features`` [B,T,2048] -> clip probability [B,1].  With ``seq_lengths`` ([B], the loaders'
+        per-clip frame counts of the zero-padded batch; train_visual.py:111) the head is fed the LSTM
+        state at each clip's own last frame instead of the state after the padding."""
+        if seq_lengths is not None:
+            _, (h_n, _) = self.lstm(features, lengths=seq_lengths)
+            lstm_out = h_n[0]
+        else:
+            lstm_out, _ = self.lstm(features)
+            lstm_out = lstm_out[:, -1, :]
         dense_out = self.fc_layers(lstm_out)
         return self.sigmoid(self.fc_out(dense_out))

@@ -36,8 +36,9 @@ class XceptionLSTMV(nn.Module):
 
     def extract_features(self, video_batch, device=None):
         """[B,T,3,H,W] -> [B,T,2048] (XceptionLSTMV.py:46-63).  ``device`` may also be the
-        ``seq_lengths`` tensor the active train_visual.py:568 passes; it is ignored
-        there, as the shipped model ignores sequence lengths."""
+        ``seq_lengths`` tensor the active train_visual.py:568 passes.  The backbone ignores it
+        and runs over the padded frames too, as the reference does (dropping frames would change
+        every BatchNorm's batch statistics); ``forward(features, seq_lengths)`` honours it."""
         if device is not None and not torch.is_tensor(device):
             self.feature_extractor.to(device)
         batch_size, seq_len, c, h, w = video_batch.shape
@@ -45,8 +46,15 @@ class XceptionLSTMV(nn.Module):
         frame_features = self.feature_extractor(frames)
         return frame_features.view(batch_size, seq_len, -1)
 
-    def forward(self, features):
-        lstm_out, _ = self.lstm(features)
-        lstm_out = lstm_out[:, -1, :]
+    def forward(self, features, seq_lengths=None):
+        """``features`` [B,T,2048] -> clip probability [B,1].  With ``seq_lengths`` ([B], the loaders'
+        per-clip frame counts of the zero-padded batch; train_visual.py:111) the head is fed the LSTM
+        state at each clip's own last frame instead of the state after the padding."""
+        if seq_lengths is not None:
+            _, (h_n, _) = self.lstm(features, lengths=seq_lengths)
+            lstm_out = h_n[0]
+        else:
+            lstm_out, _ = self.lstm(features)
+            lstm_out = lstm_out[:, -1, :]
         dense_out = self.fc_layers(lstm_out)
         return self.sigmoid(self.fc_out(dense_out))

@@ -11,30 +11,78 @@ The computation is the ``torch.ops.xcp.lstm`` custom op (xcp/torch_ops.py): the 
 projection for all T steps is one fp32 MFMA GEMM, the recurrence one fused kernel per
 direction of time (lstm.hip).  The head runs in fp32 in every precision mode (it is
 ~0.1 GFLOP per clip).
+
+Zero-padded clips of unequal length (the loaders' ``seq_lengths``) go through
+``torch.ops.xcp.lstm_varlen`` (lstm_varlen.hip), either as ``lstm(x, lengths=...)`` or as a
+``PackedSequence`` input, with the semantics of ``pack_padded_sequence`` -> ``nn.LSTM`` ->
+``pad_packed_sequence``.
 """
 import torch
 import torch.nn as nn
+from torch.nn.utils.rnn import PackedSequence, pack_padded_sequence, pad_packed_sequence
 
-from . import torch_ops  # noqa: F401  (registers torch.ops.xcp.lstm)
+from . import torch_ops  # noqa: F401  (registers torch.ops.xcp.lstm, torch.ops.xcp.lstm_varlen)
 
 
 class LSTM(nn.LSTM):
     """nn.LSTM with the xcp forward.  Supported configuration (the reference's):
     num_layers=1, batch_first=True, unidirectional, bias=True, proj_size=0, no
     initial state.  ``xcp_kernel`` (attribute): 0 = automatic recurrence kernel choice,
-    1 = the generic kernels."""
+    1 = the generic kernels.
+
+    ``forward(input, hx=None, lengths=None)``: with ``lengths`` (int32 / int64 ``[B]``) clip ``b`` is
+    ``input[b, :lengths[b]]`` and the rest of its rows is padding: ``out[b, t >= L]`` is zero, ``h_n`` /
+    ``c_n`` are the state after the clip's last real frame and the padding receives and contributes no
+    gradient.  Padded input rows must be finite (the loaders write zeros).  A CPU ``lengths`` tensor is
+    validated (``1 <= L <= T``, as ``pack_padded_sequence`` demands); a device tensor is passed to the
+    kernels unread -- they clamp it to ``[0, T]``, and a clip of length 0 gives zero outputs, states and
+    gradients -- so the call stays capturable in a HIP graph.  A ``PackedSequence`` input is unpacked,
+    run the same way and returned packed, with ``h_n`` / ``c_n`` in the caller's batch order."""
 
     xcp_kernel = 0
 
-    def forward(self, input, hx=None):  # noqa: A002  (nn.LSTM signature)
+    def forward(self, input, hx=None, lengths=None):  # noqa: A002  (nn.LSTM signature)
         if (self.num_layers != 1 or not self.batch_first or self.bidirectional or not self.bias or self.proj_size
                 or hx is not None):
             raise NotImplementedError("xcp LSTM supports the reference configuration only "
                                       "(1 layer, batch_first, unidirectional, bias, zero initial state)")
+        if isinstance(input, PackedSequence):
+            if lengths is not None:
+                raise ValueError("a PackedSequence carries its own lengths; do not pass lengths= with it")
+            return self._forward_packed(input)
         if input.dim() != 3:
             raise NotImplementedError("xcp LSTM expects batched [B, T, F] input")
+        if lengths is not None:
+            lengths = self._check_lengths(lengths, input.shape[0], input.shape[1])
         if not input.is_cuda:
             raise RuntimeError("xcp LSTM runs on the MI355X only (got a non-GPU tensor); there is no CPU fallback")
+        if lengths is not None:
+            out, hn, cn, _, _, _ = torch.ops.xcp.lstm_varlen(
+                input, self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0,
+                lengths.to(device=input.device, dtype=torch.int32).contiguous(), int(self.xcp_kernel))
+            return out.to(input.dtype), (hn, cn)
         out, hn, cn, _, _, _ = torch.ops.xcp.lstm(input, self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0,
                                                   self.bias_hh_l0, int(self.xcp_kernel))
         return out.to(input.dtype), (hn, cn)
+
+    @staticmethod
+    def _check_lengths(lengths, B, T):
+        if not torch.is_tensor(lengths) or lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError("lengths must be an int32 or int64 tensor")
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"lengths must have shape [{B}] (one per clip), got {tuple(lengths.shape)}")
+        if not lengths.is_cuda and B > 0:   # host values: pack_padded_sequence's rule; device values are clamped
+            lo, hi = int(lengths.min()), int(lengths.max())
+            if lo < 1 or hi > T:
+                raise ValueError(f"lengths must lie in [1, {T}] (the padded length), got [{lo}, {hi}]")
+        return lengths
+
+    def _forward_packed(self, packed):
+        """Compatibility path: plain torch gathers around the length-aware op."""
+        x, lens = pad_packed_sequence(packed, batch_first=True)   # caller's batch order, lens on the CPU
+        out, (hn, cn) = self.forward(x, lengths=lens)
+        si = packed.sorted_indices
+        if si is not None:
+            out, lens = out.index_select(0, si), lens.index_select(0, si.to(lens.device))
+        data = pack_padded_sequence(out, lens, batch_first=True, enforce_sorted=True).data
+        return PackedSequence(data, packed.batch_sizes, packed.sorted_indices, packed.unsorted_indices), (hn, cn)

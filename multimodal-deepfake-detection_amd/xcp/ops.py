@@ -607,3 +607,30 @@ def lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, B, T, H, kernel=0):
     _lib.call("xcp_lstm_bwd", _p(dout), _p(dhn), _p(dcn), _p(whh), _p(cst), _p(gates), _p(dgates), _p(work), B, T, H,
               kernel, stream())
 
+
+# length-aware forms (lstm_varlen.hip): lens is an int32 [B] device tensor, clamped to [0, T] by the
+# kernels and never read on the host.  H 64 / 128 register-resident, H 256-1024 the per-step kernels
+# (never the persistent ones), anything else and kernel = 1 the generic pair.
+def lstm_varlen_needs_whhT(B, H, kernel=0):
+    return _lib.call("xcp_lstm_varlen_needs_whhT", B, H, kernel) != 0
+
+
+def _check_lens(lens, ref, B):
+    if lens.dtype != torch.int32 or lens.device != ref.device or lens.shape != (B,) or not lens.is_contiguous():
+        raise ValueError(f"lens must be a contiguous int32 [{B}] tensor on {ref.device}, got {lens.dtype} "
+                         f"{tuple(lens.shape)} on {lens.device}")
+
+
+def lstm_fwd_varlen(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H, kernel=0):
+    _check_lens(lens, out, B)
+    _lib.call("xcp_lstm_fwd_varlen", _p(xproj), _p(whh), _p(whhT), _p(bih), _p(bhh), _p(out), _p(hprev), _p(cst),
+              _p(gates), _p(hn), _p(cn), _p(lens), B, T, H, kernel, stream())
+
+
+def lstm_bwd_varlen(dout, dhn, dcn, whh, cst, gates, dgates, lens, B, T, H, kernel=0):
+    _check_lens(lens, dgates, B)
+    # the per-step kernels' cell-gradient carry [B][H] + W_hh^T [H][4H] (include/xcp.h)
+    work = torch.empty(B * H + 4 * H * H, device=whh.device, dtype=torch.float32)
+    _lib.call("xcp_lstm_bwd_varlen", _p(dout), _p(dhn), _p(dcn), _p(whh), _p(cst), _p(gates), _p(dgates), _p(work),
+              _p(lens), B, T, H, kernel, stream())
+
