@@ -289,7 +289,7 @@ int xcp_lstm_fwd(const float* xproj, const float* whh, const float* whhT, const 
 int xcp_lstm_bwd(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
                  const float* gates, float* dgates, float* work, int B, int T, int H, int kernel, xcp_stream_t stream);
 
-/* ---- LSTM recurrence over zero-padded clips of unequal length (lstm_varlen.hip) ----
+/* ---- LSTM recurrence over zero-padded clips of unequal length (lstm.hip, the same kernels) ----
  * The arguments of xcp_lstm_fwd / xcp_lstm_bwd plus lens [B] (int, device memory; clamped to [0, T]
  * by the kernels, never read by the host, so a call is capturable in a HIP graph).  Semantics of
  * pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length = T): for L = lens[b],

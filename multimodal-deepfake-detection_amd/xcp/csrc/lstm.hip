@@ -9,6 +9,30 @@
 // The input projection x W_ih^T for all T steps is one MFMA GEMM (gemm.hip);
 // these kernels run the serial part: one workgroup per clip walks the T steps,
 // keeping h in LDS and reading W_hh^T (coalesced across gate lanes) from L2.
+//
+// Per-clip lengths.  The generic, register-resident and per-step kernels are templates on
+// `bool VL`: the VL = false instantiation is the fixed-length kernel (it never touches `lens`, its
+// last argument), the VL = true one takes zero-padded clips of unequal length (lens [B], int,
+// device memory; clamped here to [0, T]).  Both are one body, so with lens[b] = T the results are
+// bit-identical to the fixed-length call (tests/test_gpu_lstm_varlen.py pins that per family); where
+// the compiler could contract a cell expression differently per instantiation its roundings are
+// spelled out.  The semantics are those of pack_padded_sequence -> nn.LSTM ->
+// pad_packed_sequence(total_length = T): for clip b with L = lens[b], out[b][t] is h_t for t < L and
+// zero for t >= L, h_n / c_n are the state after step L - 1 (zero for L = 0); the backward ignores
+// dout[b][t >= L], takes dh_n / dc_n in at step L - 1 and writes zero pre-activation gradients for
+// t >= L, so the clip adds nothing to any gradient from its padding and dx[b][t >= L] is exactly
+// zero.
+//   register-resident (H = 64 / 128) and generic: one workgroup per clip, L is workgroup-uniform;
+//     the workgroup walks its clip's L steps, zero-fills its tail rows and leaves;
+//   per-step (H = 256 / 512 / 1024, B <= 32): the (clip, unit) cell threads are masked per clip.
+// A call with lengths never takes the persistent, gather or clip-grouped kernels below (H = 256 /
+// 512 go to the per-step kernels): those hand steps over through polled counters with a timeout
+// (the open findings in ADVICE.md), and nothing length-aware polls, counts or can time out.
+//
+// Saved state for t >= L: hprev is written (zero) because the weight gradient dW_hh = dgates^T hprev
+// runs over all B*T rows and 0 x (uninitialised) may be NaN; cst and gates are left unwritten there
+// and no kernel uses a value loaded from such a row (the per-step kernels load some as stand-in
+// addresses and select them away, as they do for absent operands).
 #include "common.h"
 #include <stdlib.h>
 #include <mutex>
@@ -19,23 +43,35 @@ namespace {
 
 XCP_DEV float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
+// 1 - v * v with the product rounded before the subtraction (no fma contraction)
+XCP_DEV float one_minus_sq_unfused(float v) {
+#pragma clang fp contract(off)
+  const float p = v * v;
+  return 1.f - p;
+}
+
+XCP_DEV int lstm_len(const int* __restrict__ lens, int b, int T) { return min(max(lens[b], 0), T); }
+
 // xproj [B][T][4H] (already x W_ih^T); whhT [H][4H]; bias = b_ih + b_hh added here.
 // Outputs: out/h [B][T][H], hprev [B][T][H] (h_{t-1}), c [B][T][H],
 // gates [B][T][4H] post-activation (i, f, g, o), h_n / c_n [B][H].
+template <bool VL>
 __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__ xproj, const float* __restrict__ whhT,
                                                        const float* __restrict__ bih, const float* __restrict__ bhh,
                                                        float* __restrict__ out, float* __restrict__ hprev,
                                                        float* __restrict__ cst, float* __restrict__ gates,
-                                                       float* __restrict__ hn, float* __restrict__ cn, int T, int H) {
+                                                       float* __restrict__ hn, float* __restrict__ cn, int T, int H,
+                                                       const int* __restrict__ lens) {
   extern __shared__ float sm[];   // h [H], c [H], gate pre-activations [4H]
   float* sh = sm;
   float* sc = sm + H;
   float* sg = sm + 2 * H;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int G4 = 4 * H;
+  const int L = VL ? lstm_len(lens, b, T) : T;
   for (int k = tid; k < H; k += blockDim.x) { sh[k] = 0.f; sc[k] = 0.f; }
   __syncthreads();
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < L; ++t) {
     const float* xp = xproj + ((long)b * T + t) * G4;
     for (int j = tid; j < G4; j += blockDim.x) {
       float acc = xp[j] + bih[j] + bhh[j];
@@ -65,27 +101,37 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
     hn[(long)b * H + k] = sh[k];
     cn[(long)b * H + k] = sc[k];
   }
+  if constexpr (VL) {   // tail rows t >= L (contiguous): out and hprev zero (H is arbitrary here: 4-B stores)
+    const long tb = ((long)b * T + L) * H, tn = (long)(T - L) * H;
+    for (long e = tid; e < tn; e += blockDim.x) {
+      out[tb + e] = 0.f;
+      hprev[tb + e] = 0.f;
+    }
+  }
 }
 
 // Backward through time.  dout [B][T][H] (may be null = zeros), dhn/dcn [B][H]
 // (may be null).  whh [4H][H] (row-major, as stored by nn.LSTM).
 // Writes dgates [B][T][4H] (pre-activation gradients).
+template <bool VL>
 __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ dhn,
                                                        const float* __restrict__ dcn, const float* __restrict__ whh,
                                                        const float* __restrict__ cst, const float* __restrict__ gates,
-                                                       float* __restrict__ dgates, int T, int H) {
+                                                       float* __restrict__ dgates, int T, int H,
+                                                       const int* __restrict__ lens) {
   extern __shared__ float sm[];   // dh [H], dc [H], dgates_t [4H]
   float* sdh = sm;
   float* sdc = sm + H;
   float* sdg = sm + 2 * H;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int G4 = 4 * H;
+  const int L = VL ? lstm_len(lens, b, T) : T;
   for (int k = tid; k < H; k += blockDim.x) {
     sdh[k] = dhn ? dhn[(long)b * H + k] : 0.f;
     sdc[k] = dcn ? dcn[(long)b * H + k] : 0.f;
   }
   __syncthreads();
-  for (int t = T - 1; t >= 0; --t) {
+  for (int t = L - 1; t >= 0; --t) {
     const long ob = ((long)b * T + t) * H;
     const float* gt = gates + ((long)b * T + t) * G4;
     float* dg = dgates + ((long)b * T + t) * G4;
@@ -113,6 +159,10 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
     }
     __syncthreads();
   }
+  if constexpr (VL) {   // tail rows t >= L: zero pre-activation gradients
+    const long tb = ((long)b * T + L) * G4, tn = (long)(T - L) * G4;
+    for (long e = tid; e < tn; e += blockDim.x) dgates[tb + e] = 0.f;
+  }
 }
 
 
@@ -124,19 +174,21 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
 // except the per-step x-projection / state rows, which are prefetched one step ahead.
 //
 // forward: thread (gate j, part s), tid = j*S + s, holds W_hh[j][s*KPT .. +KPT).
-template <int H>
+template <int H, bool VL>
 __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restrict__ xproj,
                                                             const float* __restrict__ whh,
                                                             const float* __restrict__ bih,
                                                             const float* __restrict__ bhh, float* __restrict__ out,
                                                             float* __restrict__ hprev, float* __restrict__ cst,
                                                             float* __restrict__ gates, float* __restrict__ hn,
-                                                            float* __restrict__ cn, int T) {
+                                                            float* __restrict__ cn, int T,
+                                                            const int* __restrict__ lens) {
   constexpr int G4 = 4 * H, S = 1024 / G4, KPT = H / S, PADK = KPT + 4;
   static_assert(S >= 1 && KPT % 4 == 0, "unsupported H");
   __shared__ __attribute__((aligned(16))) float sh[S * PADK];   // h_{t-1}, part s at s*PADK (bank-spread)
   __shared__ float sg[G4];                                      // activated gates of step t
   const int tid = threadIdx.x, b = blockIdx.x;
+  const int L = VL ? lstm_len(lens, b, T) : T;   // workgroup-uniform
   const int j = tid / S, s = tid % S;
   float w[KPT];
   const float* wp = whh + (long)j * H + s * KPT;
@@ -151,11 +203,11 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
   if (tid < H) sh[hidx(tid)] = 0.f;
   float c = 0.f;                                 // c_{t-1}[tid] for tid < H
   const float* xb = xproj + (long)b * T * G4;
-  float xn = s == 0 ? xb[j] : 0.f;
+  float xn = s == 0 ? xb[j] : 0.f;               // (row 0 exists for L = 0 too: T >= 1)
   __syncthreads();
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < L; ++t) {
     const float xc = xn;
-    if (s == 0 && t + 1 < T) xn = xb[(long)(t + 1) * G4 + j];
+    if (s == 0 && t + 1 < L) xn = xb[(long)(t + 1) * G4 + j];
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     const float* hp = sh + s * PADK;
 #pragma unroll
@@ -192,24 +244,38 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
     hn[(long)b * H + tid] = sh[hidx(tid)];
     cn[(long)b * H + tid] = c;
   }
+  if constexpr (VL) {
+    // tail rows t >= L, contiguous from row b*T + L (a multiple of H floats: 16-B aligned): out and
+    // hprev zero, one float4 per thread and pass
+    const long n4 = (long)(T - L) * (H / 4);
+    float4* po = reinterpret_cast<float4*>(out + ((long)b * T + L) * H);
+    float4* ph = reinterpret_cast<float4*>(hprev + ((long)b * T + L) * H);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long e = tid; e < n4; e += 1024) {
+      po[e] = z;
+      ph[e] = z;
+    }
+  }
 }
 
 // backward: thread (unit k, part p), tid = k*P + p, holds W_hh[p*JPT .. +JPT)[k]; the
 // step's pre-activation gradients are broadcast from LDS and dh_{t-1}[k] is reduced over
 // the P parts (adjacent lanes) by shuffles.
-template <int H>
+template <int H, bool VL>
 __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restrict__ dout,
                                                             const float* __restrict__ dhn,
                                                             const float* __restrict__ dcn,
                                                             const float* __restrict__ whh,
                                                             const float* __restrict__ cst,
                                                             const float* __restrict__ gates,
-                                                            float* __restrict__ dgates, int T) {
+                                                            float* __restrict__ dgates, int T,
+                                                            const int* __restrict__ lens) {
   constexpr int G4 = 4 * H, P = 1024 / H, JPT = G4 / P, PADJ = JPT + 4;
   static_assert(P >= 1 && JPT % 4 == 0, "unsupported H");
   __shared__ __attribute__((aligned(16))) float sdg[P * PADJ];
   __shared__ float sdh[H];
   const int tid = threadIdx.x, b = blockIdx.x;
+  const int L = VL ? lstm_len(lens, b, T) : T;   // workgroup-uniform
   const int k = tid / P, p = tid % P;
   float w[JPT];
 #pragma unroll
@@ -229,10 +295,10 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
   if (tid < H) {
     sdh[tid] = dhn ? dhn[(long)b * H + tid] : 0.f;
     dc = dcn ? dcn[(long)b * H + tid] : 0.f;
-    fetch(T - 1);
+    if (!VL || L > 0) fetch(L - 1);
   }
   __syncthreads();
-  for (int t = T - 1; t >= 0; --t) {
+  for (int t = L - 1; t >= 0; --t) {
     if (tid < H) {
       const float c = n_c, cp = n_cp, ig = n_i, fg = n_f, gg = n_g, og = n_o;
       const float dh = sdh[tid] + n_do;
@@ -265,6 +331,12 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
     if (p == 0) sdh[k] = acc;
     __syncthreads();
   }
+  if constexpr (VL) {   // tail rows t >= L (contiguous, 16-B aligned): zero pre-activation gradients
+    const long n4 = (long)(T - L) * (G4 / 4);
+    float4* pd = reinterpret_cast<float4*>(dgates + ((long)b * T + L) * G4);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long e = tid; e < n4; e += 1024) pd[e] = z;
+  }
 }
 
 
@@ -279,16 +351,21 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
 // forward step t: thread (row r = gate q of unit uu, k-slice s of H/32) dots its W_hh row
 // slice with h_{t-1} (staged in LDS, rows padded against bank conflicts) for every clip,
 // the 32 slices reduce by shuffles, and (clip, unit) threads run the cell.
+//
+// With lengths every dot product still runs for every clip (a finished clip's h_{t-1} /
+// dgates_{t+1} row is the zero this pair wrote, or the clip's last real row at t = L: finite either
+// way, and nothing of that clip is read again); only the (clip, unit) cell threads look at the
+// clip's length.
 constexpr int LS_UPW = 2;              // hidden units per workgroup
 constexpr int LS_MAXB = 32;            // clips (register partials per thread)
 
-template <int KS>   // KS = H / 32 (k values per slice)
+template <int KS, bool VL>   // KS = H / 32 (k values per slice)
 __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restrict__ xproj, const float* __restrict__ whh,
                                                             const float* __restrict__ bih, const float* __restrict__ bhh,
                                                             float* __restrict__ out, float* __restrict__ hprev,
                                                             float* __restrict__ cst, float* __restrict__ gates,
                                                             float* __restrict__ hn, float* __restrict__ cn, int B, int T,
-                                                            int t) {
+                                                            int t, const int* __restrict__ lens) {
   constexpr int H = KS * 32, G4 = 4 * H, PS = KS + 4;   // LDS slice pitch (floats)
   constexpr int RP = 33;                                // pitch of a (row, clip) partial row
   extern __shared__ float sm[];   // h_{t-1} [B][32][PS] (then the partials [8][B][RP]), then pre [8][B]
@@ -371,6 +448,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
   __syncthreads();
   if (tid < B * LS_UPW) {
     const int b = tid / LS_UPW, v = tid - b * LS_UPW, k = u0 + v;
+    const int L = VL ? lstm_len(lens, b, T) : T;
+    const bool live = !VL || t < L;   // past the clip's end: zero out / hprev, no state, no saved gates
     const float* xp = xproj + ((long)b * T + t) * G4;
     float pre[4];
 #pragma unroll
@@ -381,18 +460,23 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
     const float ig = sigm(pre[0]), fg = sigm(pre[1]), gg = tanhf(pre[2]), og = sigm(pre[3]);
     const long ob = ((long)b * T + t) * H;
     const long op = t > 0 ? ob - H + k : ob + k;   // t = 0: a valid stand-in, selected away
+    // (t > L: row t - 1 of cst was never written -- a valid address whose value is selected away)
     const float vcp = cst[op], vhp = out[op];
     const float cp = t > 0 ? vcp : 0.f;
     const float c = fmaf(fg, cp, ig * gg);
     const float h = og * tanhf(c);
     float* gt = gates + ((long)b * T + t) * G4;
-    gt[k] = ig; gt[H + k] = fg; gt[2 * H + k] = gg; gt[3 * H + k] = og;
-    hprev[ob + k] = t > 0 ? vhp : 0.f;
-    cst[ob + k] = c;
-    out[ob + k] = h;
-    if (t == T - 1) {
+    if (live) { gt[k] = ig; gt[H + k] = fg; gt[2 * H + k] = gg; gt[3 * H + k] = og; }
+    hprev[ob + k] = live && t > 0 ? vhp : 0.f;
+    if (live) cst[ob + k] = c;
+    out[ob + k] = live ? h : 0.f;
+    if (t == L - 1) {
       hn[(long)b * H + k] = h;
       cn[(long)b * H + k] = c;
+    }
+    if (VL && t == 0 && L == 0) {
+      hn[(long)b * H + k] = 0.f;
+      cn[(long)b * H + k] = 0.f;
     }
   }
 }
@@ -413,11 +497,15 @@ __global__ __launch_bounds__(256) void lstm_transpose_kernel(const float* __rest
 // t = T-1): thread (clip b, j-slice sl of 4H/16) against the workgroup's 2 W_hh columns in
 // LDS, 16-slice shuffle reduction; (clip, unit) threads run the cell backward with the cell
 // gradient carried in dcw [B][H] (each unit's carry is only touched by its workgroup).
+// With lengths, clip b at t >= L writes zero dgates (so the recurrent sum into its step L - 1
+// vanishes on its own) and leaves its carry alone; at t = L - 1 it takes dhn / dcn as a full clip
+// does at T - 1.
+template <bool VL>
 __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restrict__ dout, const float* __restrict__ dhn,
                                                             const float* __restrict__ dcn, const float* __restrict__ whhT,
                                                             const float* __restrict__ cst, const float* __restrict__ gates,
                                                             float* __restrict__ dgates, float* __restrict__ dcw, int B,
-                                                            int T, int H, int t) {
+                                                            int T, int H, int t, const int* __restrict__ lens) {
   extern __shared__ float sm[];   // W columns [16 slices][SP] ([4H / 16][2] each), dh [B][2]
   const int G4 = 4 * H;
   const int per = G4 / 16, SP = 2 * per + 4;   // slice pitch: +4 floats, so the 16 slices of a
@@ -492,10 +580,13 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
   }
   if (tid < B * LS_UPW) {
     const int b = tid / LS_UPW, v = tid - b * LS_UPW, k = u0 + v;
+    const int L = VL ? lstm_len(lens, b, T) : T;
+    const bool live = !VL || t < L;
     const long ob = ((long)b * T + t) * H, bk = (long)b * H + k;
-    // every global load unconditional (absent operands read a valid stand-in address and are
-    // selected away), so they go out together instead of one round trip per branch
-    const bool last = t == T - 1;
+    // every global load unconditional (absent operands, and every operand of a clip past its end,
+    // read a valid stand-in address and are selected away), so they go out together instead of one
+    // round trip per branch
+    const bool last = t == L - 1;
     const float* pc = cst + ob + k;
     const float vhn = *(last && dhn ? dhn + bk : pc);
     const float vcw = *(!last ? dcw + bk : (dcn ? dcn + bk : pc));
@@ -504,20 +595,26 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
     const float c = *pc;
     const float* gt = gates + ((long)b * T + t) * G4;
     const float ig = gt[k], fg = gt[H + k], gg = gt[2 * H + k], og = gt[3 * H + k];
+    // (t < T - 1 whenever !last && live, so sdh was written above)
     const float dhr = !last ? sdh[b * 2 + v] : (dhn ? vhn : 0.f);
     const float dcr = !last || dcn ? vcw : 0.f;
     const float dh = dhr + (dout ? vdo : 0.f);
     const float cp = t > 0 ? vcp : 0.f;
     const float tc = tanhf(c);
     const float dO = dh * tc;
-    const float dc = dcr + dh * og * (1.f - tc * tc);
+    // dcr + dh * og * (1 - tc * tc) with its roundings spelled out: left to the compiler, one
+    // instantiation pairs tc * tc with dh * og into a packed multiply (the product rounded before the
+    // subtraction) and the other contracts it into an fma, and full lengths would no longer be
+    // bit-identical to the call without lengths.  This is the rounding the fixed-length kernel has
+    // always had.
+    const float dc = fmaf(dh * og, one_minus_sq_unfused(tc), dcr);
     const float dI = dc * gg, dG = dc * ig, dF = dc * cp;
-    dcw[bk] = dc * fg;
+    if (live) dcw[bk] = dc * fg;
     float* dg = dgates + ((long)b * T + t) * G4;
-    dg[k] = dI * ig * (1.f - ig);
-    dg[H + k] = dF * fg * (1.f - fg);
-    dg[2 * H + k] = dG * (1.f - gg * gg);
-    dg[3 * H + k] = dO * og * (1.f - og);
+    dg[k] = live ? dI * ig * (1.f - ig) : 0.f;
+    dg[H + k] = live ? dF * fg * (1.f - fg) : 0.f;
+    dg[2 * H + k] = live ? dG * (1.f - gg * gg) : 0.f;
+    dg[3 * H + k] = live ? dO * og * (1.f - og) : 0.f;
   }
 }
 
@@ -1171,50 +1268,52 @@ int lp_sync(hipStream_t st, LstmSync& sy) {
   return XCP_OK;
 }
 
-}  // namespace
+// Forward and backward dispatch.  lens null: fixed length; non-null: per-clip lengths, which skip
+// the persistent, clip-grouped and gather kernels (those have no length-aware form).
+bool lstm_fwd_persist(int B, int H, int kernel, bool vl) { return !vl && lstm_persist(B, H, kernel, true); }
 
-
-extern "C" {
-
-// 1 when a persistent LSTM launch on any stream gave up waiting for its workgroups (its results are
-// invalid); clears the flags.  Synchronises the device.
-int xcp_lstm_sync_error() {
-  void* base = nullptr;
-  if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&base, HIP_SYMBOL(g_lstm_sync)) != hipSuccess)
-    return -1;
-  static unsigned host[64][8 * LP_SHARD + 32];
-  if (hipMemcpy(host, base, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  int any = 0;
-  for (int i = 0; i < 64; ++i)
-    if (host[i][8 * LP_SHARD]) {
-      any = 1;
-      unsigned* w = reinterpret_cast<unsigned*>(base) + (long)i * (8 * LP_SHARD + 32) + 8 * LP_SHARD;
-      if (hipMemset(w, 0, sizeof(unsigned)) != hipSuccess) return -1;
-    }
-  return any;
-}
-
-// 1 when xcp_lstm_fwd (same B, H, kernel) runs the generic kernel, which reads the transposed W_hh
-int xcp_lstm_needs_whhT(int B, int H, int kernel) {
-  // (the register-resident, persistent and per-step forward kernels read W_hh as stored)
-  return lstm_reg(H, kernel) || lstm_persist(B, H, kernel, true) || lstm_step(B, H, kernel) ? 0 : 1;
-}
-
-int xcp_lstm_fwd(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh, float* out,
-                 float* hprev, float* cst, float* gates, float* hn, float* cn, int B, int T, int H, int kernel,
-                 hipStream_t st) {
-  if (B <= 0 || T <= 0) return XCP_OK;
-  if (kernel < 0 || kernel > 1) return XCP_EINVAL;
+// the register-resident, per-step or generic forward
+template <bool VL>
+int lstm_fwd_launch(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh, float* out,
+                    float* hprev, float* cst, float* gates, float* hn, float* cn, const int* lens, int B, int T, int H,
+                    int kernel, hipStream_t st) {
   if (lstm_reg(H, kernel)) {
     if (H == 128)
-      hipLaunchKernelGGL(lstm_fwd_reg_kernel<128>, dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out, hprev, cst,
-                         gates, hn, cn, T);
+      hipLaunchKernelGGL((lstm_fwd_reg_kernel<128, VL>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out, hprev,
+                         cst, gates, hn, cn, T, lens);
     else
-      hipLaunchKernelGGL(lstm_fwd_reg_kernel<64>, dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out, hprev, cst,
-                         gates, hn, cn, T);
+      hipLaunchKernelGGL((lstm_fwd_reg_kernel<64, VL>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out, hprev,
+                         cst, gates, hn, cn, T, lens);
     return (int)hipGetLastError();
   }
-  if (lstm_persist(B, H, kernel, true)) {
+  if (lstm_step(B, H, kernel)) {
+    const size_t smem = ((size_t)B * 32 * (H / 32 + 4) + 8 * B) * sizeof(float);
+    for (int t = 0; t < T; ++t) {
+      if (H == 256)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<8, VL>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh,
+                           out, hprev, cst, gates, hn, cn, B, T, t, lens);
+      else if (H == 512)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<16, VL>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh,
+                           out, hprev, cst, gates, hn, cn, B, T, t, lens);
+      else
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<32, VL>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh,
+                           out, hprev, cst, gates, hn, cn, B, T, t, lens);
+    }
+    return (int)hipGetLastError();
+  }
+  if (!whhT) return XCP_EINVAL;
+  const size_t smem = (size_t)6 * H * sizeof(float);
+  hipLaunchKernelGGL(lstm_fwd_kernel<VL>, dim3(B), dim3(256), smem, st, xproj, whhT, bih, bhh, out, hprev, cst, gates, hn,
+                     cn, T, H, lens);
+  return (int)hipGetLastError();
+}
+
+int lstm_fwd(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh, float* out,
+             float* hprev, float* cst, float* gates, float* hn, float* cn, const int* lens, int B, int T, int H, int kernel,
+             hipStream_t st) {
+  if (B <= 0 || T <= 0) return XCP_OK;
+  if (kernel < 0 || kernel > 1) return XCP_EINVAL;
+  if (lstm_fwd_persist(B, H, kernel, lens != nullptr)) {
     LstmSync sy;
     const int rc = lp_sync(st, sy);
     if (rc != XCP_OK) return rc;
@@ -1226,32 +1325,51 @@ int xcp_lstm_fwd(const float* xproj, const float* whh, const float* whhT, const 
                          cst, gates, hn, cn, B, T, sy);
     return (int)hipGetLastError();
   }
+  return lens ? lstm_fwd_launch<true>(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H, kernel, st)
+              : lstm_fwd_launch<false>(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H, kernel, st);
+}
+
+// 1 when lstm_fwd (same B, H, kernel; vl: with lengths) runs the generic kernel, which reads the transposed W_hh
+// (the register-resident, persistent and per-step forward kernels read W_hh as stored)
+int lstm_needs_whhT(int B, int H, int kernel, bool vl) {
+  return lstm_reg(H, kernel) || lstm_fwd_persist(B, H, kernel, vl) || lstm_step(B, H, kernel) ? 0 : 1;
+}
+
+// the per-step, register-resident or generic backward
+template <bool VL>
+int lstm_bwd_launch(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
+                    const float* gates, float* dgates, float* work, const int* lens, int B, int T, int H, int kernel,
+                    hipStream_t st) {
   if (lstm_step(B, H, kernel)) {
-    const size_t smem = ((size_t)B * 32 * (H / 32 + 4) + 8 * B) * sizeof(float);
-    for (int t = 0; t < T; ++t) {
-      if (H == 256)
-        hipLaunchKernelGGL(lstm_fwd_step_kernel<8>, dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh, out,
-                           hprev, cst, gates, hn, cn, B, T, t);
-      else if (H == 512)
-        hipLaunchKernelGGL(lstm_fwd_step_kernel<16>, dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh, out,
-                           hprev, cst, gates, hn, cn, B, T, t);
-      else
-        hipLaunchKernelGGL(lstm_fwd_step_kernel<32>, dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh, out,
-                           hprev, cst, gates, hn, cn, B, T, t);
-    }
+    if (!work) return XCP_EINVAL;
+    float* whhT = work + (long)B * H;
+    hipLaunchKernelGGL(lstm_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, st, whh, whhT, H);
+    const size_t smem = ((size_t)8 * H + 64 + 2 * B) * sizeof(float);
+    for (int t = T - 1; t >= 0; --t)
+      hipLaunchKernelGGL(lstm_bwd_step_kernel<VL>, dim3(H / LS_UPW), dim3(256), smem, st, dout, dhn, dcn, whhT, cst, gates,
+                         dgates, work, B, T, H, t, lens);
     return (int)hipGetLastError();
   }
-  if (!whhT) return XCP_EINVAL;
+  if (lstm_reg(H, kernel)) {
+    if (H == 128)
+      hipLaunchKernelGGL((lstm_bwd_reg_kernel<128, VL>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
+                         dgates, T, lens);
+    else
+      hipLaunchKernelGGL((lstm_bwd_reg_kernel<64, VL>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
+                         dgates, T, lens);
+    return (int)hipGetLastError();
+  }
   const size_t smem = (size_t)6 * H * sizeof(float);
-  hipLaunchKernelGGL(lstm_fwd_kernel, dim3(B), dim3(256), smem, st, xproj, whhT, bih, bhh, out, hprev, cst, gates, hn, cn,
-                     T, H);
+  hipLaunchKernelGGL(lstm_bwd_kernel<VL>, dim3(B), dim3(256), smem, st, dout, dhn, dcn, whh, cst, gates, dgates, T, H,
+                     lens);
   return (int)hipGetLastError();
 }
 
-int xcp_lstm_bwd(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
-                 const float* gates, float* dgates, float* work, int B, int T, int H, int kernel, hipStream_t st) {
+int lstm_bwd(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst, const float* gates,
+             float* dgates, float* work, const int* lens, int B, int T, int H, int kernel, hipStream_t st) {
   if (B <= 0 || T <= 0) return XCP_OK;
   if (kernel < 0 || kernel > 1) return XCP_EINVAL;
+  const bool fixed = !lens;   // only a fixed-length call takes the persistent forms
   // clip-grouped form: cpw clips per wave, H / 4 x ceil(B / (4 cpw)) workgroups, if they can all be resident
   auto cg_grid = [&](int cpw) { return (H / LP_U) * ((B + 4 * cpw - 1) / (4 * cpw)); };
   auto cg_fits = [&](int cpw) {
@@ -1277,8 +1395,8 @@ int xcp_lstm_bwd(const float* dout, const float* dhn, const float* dcn, const fl
   // faster than the per-step kernels there.  Elsewhere the per-step kernels: at XceptionLSTMA's B 16 x H 512 the
   // two-clips-per-wave form (XCP_LSTM_BWD=cg2) is 2 % faster but needs every CU resident at once
   // (profiles/r06_lstm_cg_ab.txt)
-  if (lstm_cg_default(B, H, kernel) && 2 * cg_grid(1) <= lp_cus() && cg_fits(1)) return launch_cg(1);
-  if (lstm_persist(B, H, kernel, false)) {
+  if (fixed && lstm_cg_default(B, H, kernel) && 2 * cg_grid(1) <= lp_cus() && cg_fits(1)) return launch_cg(1);
+  if (fixed && lstm_persist(B, H, kernel, false)) {
     const int cpw = lstm_bwd_cg();
     if (cpw && cg_fits(cpw)) return launch_cg(cpw);
     LstmSync sy;
@@ -1302,28 +1420,63 @@ int xcp_lstm_bwd(const float* dout, const float* dhn, const float* dcn, const fl
                          dgates, work, B, T, sy);
     return (int)hipGetLastError();
   }
-  if (lstm_step(B, H, kernel)) {
-    if (!work) return XCP_EINVAL;
-    float* whhT = work + (long)B * H;
-    hipLaunchKernelGGL(lstm_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, st, whh, whhT, H);
-    const size_t smem = ((size_t)8 * H + 64 + 2 * B) * sizeof(float);
-    for (int t = T - 1; t >= 0; --t)
-      hipLaunchKernelGGL(lstm_bwd_step_kernel, dim3(H / LS_UPW), dim3(256), smem, st, dout, dhn, dcn, whhT, cst, gates,
-                         dgates, work, B, T, H, t);
-    return (int)hipGetLastError();
-  }
-  if (lstm_reg(H, kernel)) {
-    if (H == 128)
-      hipLaunchKernelGGL(lstm_bwd_reg_kernel<128>, dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates, dgates,
-                         T);
-    else
-      hipLaunchKernelGGL(lstm_bwd_reg_kernel<64>, dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates, dgates,
-                         T);
-    return (int)hipGetLastError();
-  }
-  const size_t smem = (size_t)6 * H * sizeof(float);
-  hipLaunchKernelGGL(lstm_bwd_kernel, dim3(B), dim3(256), smem, st, dout, dhn, dcn, whh, cst, gates, dgates, T, H);
-  return (int)hipGetLastError();
+  return lens ? lstm_bwd_launch<true>(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st)
+              : lstm_bwd_launch<false>(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st);
+}
+
+}  // namespace
+
+
+extern "C" {
+
+// 1 when a persistent LSTM launch on any stream gave up waiting for its workgroups (its results are
+// invalid); clears the flags.  Synchronises the device.
+int xcp_lstm_sync_error() {
+  void* base = nullptr;
+  if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&base, HIP_SYMBOL(g_lstm_sync)) != hipSuccess)
+    return -1;
+  static unsigned host[64][8 * LP_SHARD + 32];
+  if (hipMemcpy(host, base, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  int any = 0;
+  for (int i = 0; i < 64; ++i)
+    if (host[i][8 * LP_SHARD]) {
+      any = 1;
+      unsigned* w = reinterpret_cast<unsigned*>(base) + (long)i * (8 * LP_SHARD + 32) + 8 * LP_SHARD;
+      if (hipMemset(w, 0, sizeof(unsigned)) != hipSuccess) return -1;
+    }
+  return any;
+}
+
+// 1 when xcp_lstm_fwd (same B, H, kernel) runs the generic kernel, which reads the transposed W_hh
+int xcp_lstm_needs_whhT(int B, int H, int kernel) { return lstm_needs_whhT(B, H, kernel, false); }
+
+int xcp_lstm_fwd(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh, float* out,
+                 float* hprev, float* cst, float* gates, float* hn, float* cn, int B, int T, int H, int kernel,
+                 hipStream_t st) {
+  return lstm_fwd(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, nullptr, B, T, H, kernel, st);
+}
+
+int xcp_lstm_bwd(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
+                 const float* gates, float* dgates, float* work, int B, int T, int H, int kernel, hipStream_t st) {
+  return lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, work, nullptr, B, T, H, kernel, st);
+}
+
+// The same with per-clip lengths (lens [B], device memory; null is an error, not "fixed length").
+int xcp_lstm_varlen_needs_whhT(int B, int H, int kernel) { return lstm_needs_whhT(B, H, kernel, true); }
+
+int xcp_lstm_fwd_varlen(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh,
+                        float* out, float* hprev, float* cst, float* gates, float* hn, float* cn, const int* lens, int B,
+                        int T, int H, int kernel, hipStream_t st) {
+  if (B > 0 && T > 0 && (H <= 0 || !lens)) return XCP_EINVAL;
+  return lstm_fwd(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H, kernel, st);
+}
+
+int xcp_lstm_bwd_varlen(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
+                        const float* gates, float* dgates, float* work, const int* lens, int B, int T, int H, int kernel,
+                        hipStream_t st) {
+  if (B > 0 && T > 0 && (H <= 0 || !lens)) return XCP_EINVAL;
+  return lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st);
 }
 
 }  // extern "C"
+

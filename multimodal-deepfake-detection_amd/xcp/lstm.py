@@ -13,7 +13,7 @@ direction of time (lstm.hip).  The head runs in fp32 in every precision mode (it
 ~0.1 GFLOP per clip).
 
 Zero-padded clips of unequal length (the loaders' ``seq_lengths``) go through
-``torch.ops.xcp.lstm_varlen`` (lstm_varlen.hip), either as ``lstm(x, lengths=...)`` or as a
+``torch.ops.xcp.lstm_varlen`` (the same kernels in lstm.hip), either as ``lstm(x, lengths=...)`` or as a
 ``PackedSequence`` input, with the semantics of ``pack_padded_sequence`` -> ``nn.LSTM`` ->
 ``pad_packed_sequence``.
 """

@@ -584,35 +584,11 @@ def clock_probe(device, launches=8, iters=40000):
 
 # ---------------------------------------------------------------- LSTM
 # kernel: 0 = automatic (register-resident for H 64 / 128, per-step kernels for H 256-1024),
-# 1 = the generic kernels (tests pin them at shapes the specialised kernels also cover)
-def lstm_needs_whhT(B, H, kernel=0):
-    return _lib.call("xcp_lstm_needs_whhT", B, H, kernel) != 0
-
-
-def lstm_fwd(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, B, T, H, kernel=0):
-    _lib.call("xcp_lstm_fwd", _p(xproj), _p(whh), _p(whhT), _p(bih), _p(bhh), _p(out), _p(hprev), _p(cst), _p(gates), _p(hn),
-              _p(cn), B, T, H, kernel, stream())
-
-
-def lstm_sync_error():
-    """1 if a persistent LSTM launch gave up waiting for its workgroups since the last call (its
-    outputs are invalid then), else 0; synchronises the device and clears the flags."""
-    return _lib.call("xcp_lstm_sync_error")
-
-
-def lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, B, T, H, kernel=0):
-    # per-step kernels: cell-gradient carry [B][H] + W_hh^T [H][4H]; persistent kernels: the dh partials
-    # [2][B][H / 4][H / 4][4] (include/xcp.h)
-    work = torch.empty(max(B * H + 4 * H * H, B * H * H // 2), device=whh.device, dtype=torch.float32)
-    _lib.call("xcp_lstm_bwd", _p(dout), _p(dhn), _p(dcn), _p(whh), _p(cst), _p(gates), _p(dgates), _p(work), B, T, H,
-              kernel, stream())
-
-
-# length-aware forms (lstm_varlen.hip): lens is an int32 [B] device tensor, clamped to [0, T] by the
-# kernels and never read on the host.  H 64 / 128 register-resident, H 256-1024 the per-step kernels
-# (never the persistent ones), anything else and kernel = 1 the generic pair.
-def lstm_varlen_needs_whhT(B, H, kernel=0):
-    return _lib.call("xcp_lstm_varlen_needs_whhT", B, H, kernel) != 0
+# 1 = the generic kernels (tests pin them at shapes the specialised kernels also cover).
+# lens: None, or the per-clip lengths as an int32 [B] device tensor, clamped to [0, T] by the kernels
+# and never read on the host; a call with lengths never takes the persistent kernels (lstm.hip).
+def lstm_needs_whhT(B, H, kernel=0, lens=None):
+    return _lib.call("xcp_lstm_needs_whhT" if lens is None else "xcp_lstm_varlen_needs_whhT", B, H, kernel) != 0
 
 
 def _check_lens(lens, ref, B):
@@ -621,16 +597,31 @@ def _check_lens(lens, ref, B):
                          f"{tuple(lens.shape)} on {lens.device}")
 
 
-def lstm_fwd_varlen(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H, kernel=0):
-    _check_lens(lens, out, B)
-    _lib.call("xcp_lstm_fwd_varlen", _p(xproj), _p(whh), _p(whhT), _p(bih), _p(bhh), _p(out), _p(hprev), _p(cst),
-              _p(gates), _p(hn), _p(cn), _p(lens), B, T, H, kernel, stream())
+def lstm_fwd(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, B, T, H, kernel=0, lens=None):
+    ptrs = [_p(t) for t in (xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn)]
+    if lens is None:
+        _lib.call("xcp_lstm_fwd", *ptrs, B, T, H, kernel, stream())
+    else:
+        _check_lens(lens, out, B)
+        _lib.call("xcp_lstm_fwd_varlen", *ptrs, _p(lens), B, T, H, kernel, stream())
 
 
-def lstm_bwd_varlen(dout, dhn, dcn, whh, cst, gates, dgates, lens, B, T, H, kernel=0):
-    _check_lens(lens, dgates, B)
-    # the per-step kernels' cell-gradient carry [B][H] + W_hh^T [H][4H] (include/xcp.h)
-    work = torch.empty(B * H + 4 * H * H, device=whh.device, dtype=torch.float32)
-    _lib.call("xcp_lstm_bwd_varlen", _p(dout), _p(dhn), _p(dcn), _p(whh), _p(cst), _p(gates), _p(dgates), _p(work),
-              _p(lens), B, T, H, kernel, stream())
+def lstm_sync_error():
+    """1 if a persistent LSTM launch gave up waiting for its workgroups since the last call (its
+    outputs are invalid then), else 0; synchronises the device and clears the flags."""
+    return _lib.call("xcp_lstm_sync_error")
+
+
+def lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, B, T, H, kernel=0, lens=None):
+    # per-step kernels: cell-gradient carry [B][H] + W_hh^T [H][4H]; persistent kernels (never with lengths):
+    # the dh partials [2][B][H / 4][H / 4][4] (include/xcp.h)
+    n = B * H + 4 * H * H
+    work = torch.empty(n if lens is not None else max(n, B * H * H // 2), device=whh.device, dtype=torch.float32)
+    ptrs = [_p(t) for t in (dout, dhn, dcn, whh, cst, gates, dgates, work)]
+    if lens is None:
+        _lib.call("xcp_lstm_bwd", *ptrs, B, T, H, kernel, stream())
+    else:
+        _check_lens(lens, dgates, B)
+        _lib.call("xcp_lstm_bwd_varlen", *ptrs, _p(lens), B, T, H, kernel, stream())
+
 

@@ -419,13 +419,13 @@ stem_conv2.register_autograd(_c2_bwd, setup_context=_c2_setup)
 
 
 # ------------------------------------------------------------------ LSTM (nn.LSTM, 1 layer, batch_first)
-@torch.library.custom_op("xcp::lstm", mutates_args=(), device_types="cuda")
-def lstm(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor,
-         kernel: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """nn.LSTM(I, H, 1, batch_first=True) forward (XceptionLSTMV.py:18-23, :67; gates i, f, g, o;
-    h0 = c0 = 0): the input projection of all T steps is one fp32 MFMA GEMM, the recurrence one
-    fused kernel per time direction (lstm.hip).  Returns (out [B,T,H], h_n [1,B,H], c_n [1,B,H]) and
-    the saved state (h_{t-1}, c_t [B,T,H], activated gates [B,T,4H]) for the backward."""
+# xcp::lstm / xcp::lstm_backward and their forms with per-clip lengths, xcp::lstm_varlen /
+# xcp::lstm_varlen_backward, are the same code: the helpers below take lengths=None for the former.
+_LstmOut = Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]
+_LstmGrads = Tuple[Tensor, Tensor, Tensor, Tensor]
+
+
+def _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel, lengths=None):
     with ops.device_guard(x):
         ops.check_gpu(x, w_ih)
         B, T, I = x.shape
@@ -436,7 +436,7 @@ def lstm(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor,
         ops.gemm_nt(xf, w_ih.detach().float().contiguous(), xproj, B * T, 4 * H, I)
         whh = w_hh.detach().float().contiguous()
         whhT = None
-        if ops.lstm_needs_whhT(B, H, kernel):
+        if ops.lstm_needs_whhT(B, H, kernel, lengths):
             whhT = torch.empty(H * 4 * H, device=dev, dtype=torch.float32)
             ops.permute3(whh, whhT, 4 * H, H, 1, (1, 0, 2))
         out = torch.empty(B, T, H, device=dev, dtype=torch.float32)
@@ -446,12 +446,11 @@ def lstm(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor,
         hn = torch.empty(1, B, H, device=dev, dtype=torch.float32)
         cn = torch.empty(1, B, H, device=dev, dtype=torch.float32)
         ops.lstm_fwd(xproj, whh, whhT, b_ih.detach().float().contiguous(), b_hh.detach().float().contiguous(), out,
-                     hprev, cst, gates, hn, cn, B, T, H, kernel)
+                     hprev, cst, gates, hn, cn, B, T, H, kernel, lengths)
         return out, hn, cn, hprev, cst, gates
 
 
-@lstm.register_fake
-def _(x, w_ih, w_hh, b_ih, b_hh, kernel):
+def _lstm_forward_fake(x, w_hh):
     B, T, _ = x.shape
     H = w_hh.shape[1]
     f = dict(device=x.device, dtype=torch.float32)
@@ -459,10 +458,7 @@ def _(x, w_ih, w_hh, b_ih, b_hh, kernel):
             torch.empty(B, T, H, **f), torch.empty(B, T, 4 * H, **f))
 
 
-@torch.library.custom_op("xcp::lstm_backward", mutates_args=(), device_types="cuda")
-def lstm_backward(dout: Optional[Tensor], dhn: Optional[Tensor], dcn: Optional[Tensor], x: Tensor, w_ih: Tensor,
-                  w_hh: Tensor, hprev: Tensor, cst: Tensor, gates: Tensor, kernel: int,
-                  need_dx: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+def _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx, lengths=None):
     with ops.device_guard(x):
         B, T, I = x.shape
         H = w_hh.shape[1]
@@ -472,7 +468,7 @@ def lstm_backward(dout: Optional[Tensor], dhn: Optional[Tensor], dcn: Optional[T
         dgates = torch.empty(M, 4 * H, device=dev, dtype=torch.float32)
         f32 = lambda t: None if t is None else t.float().contiguous()   # noqa: E731
         ops.lstm_bwd(f32(dout), f32(dhn), f32(dcn), w_hh.detach().float().contiguous(), cst, gates, dgates, B, T, H,
-                     kernel)
+                     kernel, lengths)
         dw_ih = torch.empty(4 * H, I, device=dev, dtype=torch.float32)
         ops.weight_grad(dgates, xf, M, 4 * H, I, dw_ih)
         dw_hh = torch.empty(4 * H, H, device=dev, dtype=torch.float32)
@@ -489,8 +485,7 @@ def lstm_backward(dout: Optional[Tensor], dhn: Optional[Tensor], dcn: Optional[T
         return dx, dw_ih, dw_hh, db
 
 
-@lstm_backward.register_fake
-def _(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx):
+def _lstm_backward_fake(x, w_ih, w_hh, need_dx):
     B, T, I = x.shape
     f = dict(device=x.device, dtype=torch.float32)
     return (torch.empty(B, T, I, **f) if need_dx else torch.empty(0, **f), torch.empty(w_ih.shape, **f),
@@ -498,126 +493,82 @@ def _(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx):
 
 
 def _lstm_setup(ctx, inputs, output):
-    x, w_ih, w_hh, b_ih, b_hh, kernel = inputs
+    x, w_ih, w_hh, b_ih, b_hh, *lengths, kernel = inputs   # lengths: [] or [lengths]
     out, hn, cn, hprev, cst, gates = output
-    ctx.save_for_backward(x, w_ih, w_hh, hprev, cst, gates)
+    ctx.save_for_backward(x, w_ih, w_hh, hprev, cst, gates, *lengths)
     ctx.kernel = kernel
     ctx.x_dtype = x.dtype
     ctx.mark_non_differentiable(hprev, cst, gates)
 
 
 def _lstm_bwd(ctx, dout, dhn, dcn, *_):
-    x, w_ih, w_hh, hprev, cst, gates = ctx.saved_tensors
+    x, w_ih, w_hh, hprev, cst, gates, *lengths = ctx.saved_tensors
     need_dx = ctx.needs_input_grad[0]
-    dx, dw_ih, dw_hh, db = torch.ops.xcp.lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, ctx.kernel,
-                                                       need_dx)
-    return (dx.to(ctx.x_dtype) if need_dx else None, dw_ih, dw_hh, db, db.clone(), None)
+    op = torch.ops.xcp.lstm_varlen_backward if lengths else torch.ops.xcp.lstm_backward
+    dx, dw_ih, dw_hh, db = op(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, *lengths, ctx.kernel, need_dx)
+    return (dx.to(ctx.x_dtype) if need_dx else None, dw_ih, dw_hh, db, db.clone(), *(None for _ in lengths), None)
+
+
+@torch.library.custom_op("xcp::lstm", mutates_args=(), device_types="cuda")
+def lstm(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, kernel: int) -> _LstmOut:
+    """nn.LSTM(I, H, 1, batch_first=True) forward (XceptionLSTMV.py:18-23, :67; gates i, f, g, o;
+    h0 = c0 = 0): the input projection of all T steps is one fp32 MFMA GEMM, the recurrence one
+    fused kernel per time direction (lstm.hip).  Returns (out [B,T,H], h_n [1,B,H], c_n [1,B,H]) and
+    the saved state (h_{t-1}, c_t [B,T,H], activated gates [B,T,4H]) for the backward."""
+    return _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel)
+
+
+@lstm.register_fake
+def _(x, w_ih, w_hh, b_ih, b_hh, kernel):
+    return _lstm_forward_fake(x, w_hh)
+
+
+@torch.library.custom_op("xcp::lstm_backward", mutates_args=(), device_types="cuda")
+def lstm_backward(dout: Optional[Tensor], dhn: Optional[Tensor], dcn: Optional[Tensor], x: Tensor, w_ih: Tensor,
+                  w_hh: Tensor, hprev: Tensor, cst: Tensor, gates: Tensor, kernel: int, need_dx: bool) -> _LstmGrads:
+    return _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx)
+
+
+@lstm_backward.register_fake
+def _(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx):
+    return _lstm_backward_fake(x, w_ih, w_hh, need_dx)
 
 
 lstm.register_autograd(_lstm_bwd, setup_context=_lstm_setup)
 
 
-# ------------------------------------------------------------------ LSTM over zero-padded clips of unequal length
 @torch.library.custom_op("xcp::lstm_varlen", mutates_args=(), device_types="cuda")
 def lstm_varlen(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, lengths: Tensor,
-                kernel: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+                kernel: int) -> _LstmOut:
     """``xcp::lstm`` with per-clip lengths (int32 [B], on x's device; clamped to [0, T] by the kernels and
     never copied to the host, so a step with lengths stays capturable in a HIP graph).  The semantics of
     pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length=T): out[b, t >= L] = 0 and
-    h_n / c_n are the state after step L - 1 (lstm_varlen.hip).  Of the saved state, hprev is zero past a
+    h_n / c_n are the state after step L - 1 (lstm.hip).  Of the saved state, hprev is zero past a
     clip's end; cst and gates are unwritten there and never read by the backward."""
-    with ops.device_guard(x):
-        ops.check_gpu(x, w_ih)
-        B, T, I = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        xf = x.detach().float().contiguous()
-        xproj = torch.empty(B * T, 4 * H, device=dev, dtype=torch.float32)
-        ops.gemm_nt(xf, w_ih.detach().float().contiguous(), xproj, B * T, 4 * H, I)
-        whh = w_hh.detach().float().contiguous()
-        whhT = None
-        if ops.lstm_varlen_needs_whhT(B, H, kernel):
-            whhT = torch.empty(H * 4 * H, device=dev, dtype=torch.float32)
-            ops.permute3(whh, whhT, 4 * H, H, 1, (1, 0, 2))
-        out = torch.empty(B, T, H, device=dev, dtype=torch.float32)
-        hprev = torch.empty(B, T, H, device=dev, dtype=torch.float32)
-        cst = torch.empty(B, T, H, device=dev, dtype=torch.float32)
-        gates = torch.empty(B, T, 4 * H, device=dev, dtype=torch.float32)
-        hn = torch.empty(1, B, H, device=dev, dtype=torch.float32)
-        cn = torch.empty(1, B, H, device=dev, dtype=torch.float32)
-        ops.lstm_fwd_varlen(xproj, whh, whhT, b_ih.detach().float().contiguous(), b_hh.detach().float().contiguous(),
-                            out, hprev, cst, gates, hn, cn, lengths, B, T, H, kernel)
-        return out, hn, cn, hprev, cst, gates
+    return _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel, lengths)
 
 
 @lstm_varlen.register_fake
 def _(x, w_ih, w_hh, b_ih, b_hh, lengths, kernel):
-    B, T, _ = x.shape
-    H = w_hh.shape[1]
-    f = dict(device=x.device, dtype=torch.float32)
-    return (torch.empty(B, T, H, **f), torch.empty(1, B, H, **f), torch.empty(1, B, H, **f), torch.empty(B, T, H, **f),
-            torch.empty(B, T, H, **f), torch.empty(B, T, 4 * H, **f))
+    return _lstm_forward_fake(x, w_hh)
 
 
 @torch.library.custom_op("xcp::lstm_varlen_backward", mutates_args=(), device_types="cuda")
 def lstm_varlen_backward(dout: Optional[Tensor], dhn: Optional[Tensor], dcn: Optional[Tensor], x: Tensor, w_ih: Tensor,
                          w_hh: Tensor, hprev: Tensor, cst: Tensor, gates: Tensor, lengths: Tensor, kernel: int,
-                         need_dx: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+                         need_dx: bool) -> _LstmGrads:
     """The pre-activation gradients are exactly zero past each clip's end, so the weight-gradient GEMMs, the
     bias sum and the dx GEMM run over all B*T rows as in ``xcp::lstm_backward`` and the padding adds exact
     zeros (the padded x rows and the saved hprev rows there are finite)."""
-    with ops.device_guard(x):
-        B, T, I = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        M = B * T
-        xf = x.detach().float().contiguous()
-        dgates = torch.empty(M, 4 * H, device=dev, dtype=torch.float32)
-        f32 = lambda t: None if t is None else t.float().contiguous()   # noqa: E731
-        ops.lstm_bwd_varlen(f32(dout), f32(dhn), f32(dcn), w_hh.detach().float().contiguous(), cst, gates, dgates,
-                            lengths, B, T, H, kernel)
-        dw_ih = torch.empty(4 * H, I, device=dev, dtype=torch.float32)
-        ops.weight_grad(dgates, xf, M, 4 * H, I, dw_ih)
-        dw_hh = torch.empty(4 * H, H, device=dev, dtype=torch.float32)
-        ops.weight_grad(dgates, hprev, M, 4 * H, H, dw_hh)
-        db = torch.empty(4 * H, device=dev, dtype=torch.float32)
-        ops.reduce_slabs(dgates, M, 4 * H, db)
-        if need_dx:
-            wT = torch.empty(I * 4 * H, device=dev, dtype=torch.float32)
-            ops.permute3(w_ih.detach().float().contiguous(), wT, 4 * H, I, 1, (1, 0, 2))
-            dx = torch.empty(B, T, I, device=dev, dtype=torch.float32)
-            ops.gemm_nt(dgates, wT, dx, M, I, 4 * H)
-        else:
-            dx = torch.empty(0, device=dev, dtype=torch.float32)
-        return dx, dw_ih, dw_hh, db
+    return _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx, lengths)
 
 
 @lstm_varlen_backward.register_fake
 def _(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, lengths, kernel, need_dx):
-    B, T, I = x.shape
-    f = dict(device=x.device, dtype=torch.float32)
-    return (torch.empty(B, T, I, **f) if need_dx else torch.empty(0, **f), torch.empty(w_ih.shape, **f),
-            torch.empty(w_hh.shape, **f), torch.empty(w_ih.shape[0], **f))
+    return _lstm_backward_fake(x, w_ih, w_hh, need_dx)
 
 
-def _lstm_vl_setup(ctx, inputs, output):
-    x, w_ih, w_hh, b_ih, b_hh, lengths, kernel = inputs
-    out, hn, cn, hprev, cst, gates = output
-    ctx.save_for_backward(x, w_ih, w_hh, hprev, cst, gates, lengths)
-    ctx.kernel = kernel
-    ctx.x_dtype = x.dtype
-    ctx.mark_non_differentiable(hprev, cst, gates)
-
-
-def _lstm_vl_bwd(ctx, dout, dhn, dcn, *_):
-    x, w_ih, w_hh, hprev, cst, gates, lengths = ctx.saved_tensors
-    need_dx = ctx.needs_input_grad[0]
-    dx, dw_ih, dw_hh, db = torch.ops.xcp.lstm_varlen_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, lengths,
-                                                              ctx.kernel, need_dx)
-    return (dx.to(ctx.x_dtype) if need_dx else None, dw_ih, dw_hh, db, db.clone(), None, None)
-
-
-lstm_varlen.register_autograd(_lstm_vl_bwd, setup_context=_lstm_vl_setup)
+lstm_varlen.register_autograd(_lstm_bwd, setup_context=_lstm_setup)
 
 
 OPS: List[str] = ["dwconv3x3", "dwconv3x3_backward", "pointwise", "pointwise_backward", "batch_norm",

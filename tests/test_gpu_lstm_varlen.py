@@ -1,4 +1,4 @@
-"""Variable-length clips through ``xcp.lstm.LSTM`` (lstm_varlen.hip) against ``torch.nn.LSTM`` on the CPU in
+"""Variable-length clips through ``xcp.lstm.LSTM`` (lstm.hip with lengths) against ``torch.nn.LSTM`` on the CPU in
 fp32 fed ``pack_padded_sequence(..., enforce_sorted=False)``, weights copied from the module under test.
 Tolerances are those of test_gpu_kernels.py::test_lstm_module_vs_oracle: out / h_n / c_n rtol 1e-4,
 atol 1e-5; dx and the parameter gradients rtol 1e-3, atol 1e-5.  The backward is driven by one seeded
@@ -126,14 +126,26 @@ def test_parity_by_kernel_family(gpu, case):
     assert_close(got, ref)
 
 
-@pytest.mark.parametrize("H", [64, 128, 256, 512])
-def test_full_lengths_equal_fixed_path_bitwise(gpu, monkeypatch, H):
+BITWISE = {   # H, B, T, kernel: every kernel family that exists with and without lengths
+    "64": (64, 3, 5, 0),                # register-resident
+    "128": (128, 3, 5, 0),
+    "256": (256, 3, 5, 0),              # per-step, KS = 8
+    "512": (512, 3, 5, 0),              # per-step, KS = 16
+    "1024": (1024, 3, 4, 0),            # per-step, KS = 32
+    "128-generic": (128, 3, 5, 1),      # the generic pair, pinned
+    "96": (96, 3, 5, 0),                # generic by shape: an H no special kernel takes
+    "256-B17": (256, 17, 5, 0),         # crosses the per-step backward's 16-clip pass
+}
+
+
+@pytest.mark.parametrize("case", list(BITWISE))
+def test_full_lengths_equal_fixed_path_bitwise(gpu, monkeypatch, case):
     """lengths = [T] * B is bit-identical to the call without lengths in every output and gradient: the
-    length-aware kernels are the same arithmetic.  (H 256 / 512: XCP_LSTM_PERSIST=0, so the call without
+    two are instantiations of one kernel body.  (H 256 / 512: XCP_LSTM_PERSIST=0, so the call without
     lengths runs the per-step kernels too.)"""
     monkeypatch.setenv("XCP_LSTM_PERSIST", "0")
-    B, T = 3, 5
-    lstm = make_lstm(H, gpu)
+    H, B, T, kernel = BITWISE[case]
+    lstm = make_lstm(H, gpu, kernel)
     x, *cot = make_inputs(B, T, H, [T] * B)
     fixed = run_xcp(lstm, x, cot, gpu)
     full = run_xcp(lstm, x, cot, gpu, lengths=torch.tensor([T] * B))
