@@ -107,7 +107,6 @@ struct NTArgs {
   float* stats;           // [gridM][2][N] partial (sum, sumsq) or nullptr
   Gather ga;
   int tqs;                // gemm_nt256p_kernel: tile-queue slot + 1 (0: static tile walk)
-  int nsplit;             // gemm_nt256p_kernel: the last nsplit tiles are walked as 2 half tiles each, first
   int khalf;              // gemm_nt256p_kernel: a last K-tile with K % 64 in (0, 32] multiplies its first half only
 };
 
@@ -123,12 +122,8 @@ constexpr int NBN = 128;
 
 template <int N>
 XCP_DEV void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else static_assert(N == 0, "unsupported count");
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit count");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 template <typename T, int GM, int WMW, int STAGES>
@@ -622,7 +617,7 @@ typedef int i32x2 __attribute__((ext_vector_type(2)));
 // the range check was seen to retire its vmcnt ahead of older loads, which a counted wait cannot allow for)
 template <bool STATS, typename Get, bool FENCE = false, bool SKIP = false>
 XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC, __amdgpu_buffer_rsrc_t rS, int m0,
-                            int n0, int wr, int wc, int fr, int fg, int side = 0) {
+                            int n0, int wr, int wc, int fr, int fg) {
   int issued = 0;
   const int bm = m0 / 256, stat_rows = (a.M + 127) / 128;
   const int mrow = m0 + wr * 128 + fr;
@@ -657,9 +652,8 @@ XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
     const uint4 st0 = odd ? make_uint4(rc0.x, rc0.y, pc[1].x, pc[1].y) : make_uint4(pc[0].x, pc[0].y, rc0.x, rc0.y);
     const uint4 st1 = odd ? make_uint4(rc1.x, rc1.y, pc[3].x, pc[3].y) : make_uint4(pc[2].x, pc[2].y, rc1.x, rc1.y);
     const unsigned rowb = (unsigned)((long)m * a.ldc * 2);
-    // (a half tile stores only its side: st0 holds the left 32 columns of the wave, st1 the right 32)
-    const unsigned o0 = (mok && c0 < a.N && side != 2) ? rowb + (unsigned)c0 * 2 : BUF_OOB;
-    const unsigned o1 = (mok && c0 + 32 < a.N && side != 1) ? rowb + (unsigned)(c0 + 32) * 2 : BUF_OOB;
+    const unsigned o0 = (mok && c0 < a.N) ? rowb + (unsigned)c0 * 2 : BUF_OOB;
+    const unsigned o1 = (mok && c0 + 32 < a.N) ? rowb + (unsigned)(c0 + 32) * 2 : BUF_OOB;
     // non-temporal (nt) C stores: the tile's 128 KB leave as streaming writes, so the round's 32 MB burst does
     // not sit in the L2s as ordinary dirty lines ahead of the next kernel's reads (the depthwise forward that
     // reads this output ran 0.433 -> 0.48 of HBM in the step, the op itself 130 -> 125 us, the step +0.9 %;
@@ -695,8 +689,7 @@ XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
     for (int q = 0; q < 2; ++q) v2[q] = (b0 ? v4[2 + q] : v4[q]) + __shfl_xor(b0 ? v4[q] : v4[2 + q], 1, 64);
     const int col = ncol + ((fr & 7) >> 1) * 16 + fg * 4 + (fr & 1) * 2;
     const int srow = bm * 2 + wr;
-    const bool sok = side == 0 || (side == 1) == (((fr & 7) >> 1) < 2);   // (a half tile: its side's columns)
-    const unsigned so = (srow < stat_rows && col < a.N && sok)
+    const unsigned so = (srow < stat_rows && col < a.N)
                             ? (unsigned)((((long)srow * 2 + (fr >> 3)) * a.N + col) * 4) : BUF_OOB;
     if (!SKIP || (bm * 2 + wr < stat_rows && ncol < a.N)) {
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, make_float2(v2[0], v2[1])), rS, (int)so, 0, 0);
@@ -708,8 +701,8 @@ XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
 
 template <bool STATS>
 XCP_DEV void epilogue256_buf(f32x4 (&acc)[8][4], const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
-                             __amdgpu_buffer_rsrc_t rS, int m0, int n0, int wr, int wc, int fr, int fg, int side = 0) {
-  epilogue256_get<STATS>([&](int i, int j, int r) { return acc[i][j][r]; }, a, rC, rS, m0, n0, wr, wc, fr, fg, side);
+                             __amdgpu_buffer_rsrc_t rS, int m0, int n0, int wr, int wc, int fr, int fg) {
+  epilogue256_get<STATS>([&](int i, int j, int r) { return acc[i][j][r]; }, a, rC, rS, m0, n0, wr, wc, fr, fg);
 }
 
 // Tile counters of the persistent NT kernel, one per (device, stream) slot: a workgroup takes its first
@@ -720,15 +713,7 @@ XCP_DEV void epilogue256_buf(f32x4 (&acc)[8][4], const NTArgs& a, __amdgpu_buffe
 // last and resets the counter for the next launch (graph replays included).
 __device__ int g_nt_tq[64];
 
-// PF2 (opt-in, XCP_NT_PF2=1; C bitwise equal, but the step measured 0.4-0.6 % slower and the in-step
-// middle-flow op 754 -> 738 TFLOP/s, the K = 128 entry shapes up to 11 % slower alone:
-// profiles/r06_nt_pf2_ab.txt): at a tile boundary the next tile's first TWO K-tiles (both ring slots) are issued ahead of this tile's
-// epilogue stores, so the stores stay in flight through the next tile's K-tile 0 and most of K-tile 1 (the
-// first wait that retires them is K-tile 1's phase Q3) instead of K-tile 0's Q3: the round's 32 MB store
-// burst gets two K-tiles to drain instead of one.  (The first tile has no stores ahead of it: its waits
-// count without them.  Dropped out-of-range stores in their place measured wrong C: their counts may retire
-// ahead of older loads.)
-template <bool STATS, bool HALF, bool PF2>
+template <bool STATS>
 __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
   constexpr int S_ST = 16 + (STATS ? 1 : 0);   // store instructions per wave per epilogue
   // (+ 16 B for the tile-queue broadcast: in the ring's LDS object, since a second object would give the
@@ -738,21 +723,6 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
   int* const tq = a.tqs > 0 ? g_nt_tq + (a.tqs - 1) : nullptr;
   const int gridN = (a.N + 255) / 256, gridM = (a.M + 255) / 256;
   const int tiles = gridM * gridN, nwg = gridDim.x;
-  // work items: the last nsplit tiles as 2 half tiles each (side 1: the B-left 32 columns of every wave's 64,
-  // side 2: the B-right 32), walked FIRST, then the other tiles whole (side 0).  A half tile runs only its
-  // side's two quadrant phases, so the workgroups that start with one reach their tile boundaries (and their
-  // epilogue stores) about half a tile out of step with the rest: the rounds' store bursts no longer coincide.
-  const int nsplit = HALF ? a.nsplit : 0, nhalf = 2 * nsplit, items = tiles + nsplit;
-  auto item_tile = [&](int it, int& side) {
-    if constexpr (HALF) {
-      if (it < nhalf) {
-        side = 1 + (it & 1);
-        return tiles - nsplit + (it >> 1);
-      }
-    }
-    side = 0;
-    return it - nhalf;
-  };
   const int slot = xcd_remap(blockIdx.x, nwg);
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: LDS-DMA destinations (M0) from SGPRs
   const int wr = w >> 2, wc = w & 3;
@@ -776,15 +746,14 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
   const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(STATS ? (void*)a.stats : a.C, (short)0,
                                                                        BUF_RECORDS, BUF_DWORD3);
   unsigned voff[4][2];
-  auto set_tile = [&](int m0, int n0, int side) {
+  auto set_tile = [&](int m0, int n0) {
 #pragma unroll
     for (int h = 0; h < 4; ++h)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const bool isA = (h == 0 || h == 3);
         const int r = (isA ? m0 : n0) + rowt[h][i];
-        // (a half tile's other B half is not fetched: its DMA slots load the zero line)
-        const bool ok = (isA ? r < a.M : r < a.N) && !(HALF && ((h == 1 && side == 2) || (h == 2 && side == 1)));
+        const bool ok = isA ? r < a.M : r < a.N;
         voff[h][i] = ok ? (unsigned)(((long)r * (isA ? a.lda : a.ldb) + kc8[h][i]) * 2) : BUF_OOB;
       }
   };
@@ -823,45 +792,30 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
               __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j][ks], af[i][ks], acc[ih * 4 + i][jh * 2 + j], 0, 0, 0);
     }
   };
-  int side = 0;   // of the current item (wave-uniform)
   auto sync_mfma = [&](int ih, const bf16x8 (&b)[2][2], int jh, auto nks) {
     __builtin_amdgcn_s_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if (!HALF || side != 2 - jh) {   // (a half tile skips the other side's quadrants)
-      __builtin_amdgcn_s_setprio(1);
-      mfma_q(ih, b, jh, nks);
-      __builtin_amdgcn_s_setprio(0);
-    }
+    __builtin_amdgcn_s_setprio(1);
+    mfma_q(ih, b, jh, nks);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
   };
 
   int t = slot;
-  if (t >= items) return;
-  int tile = item_tile(t, side);
-  int m0 = (tile / gridN) * 256, n0 = (tile % gridN) * 256;
-  set_tile(m0, n0, side);
+  if (t >= tiles) return;
+  int m0 = (t / gridN) * 256, n0 = (t % gridN) * 256;
+  set_tile(m0, n0);
 #pragma unroll
   for (int h = 0; h < 4; ++h) issue(h, 0);
-  if constexpr (PF2) {
-    if (nk > 1)
-#pragma unroll
-      for (int h = 0; h < 4; ++h) issue(h, 1);
-  }
-  int extra = 0;   // epilogue stores of the previous tile still allowed in flight during K-tile 0
+  int extra = 0;   // the previous tile's epilogue stores may still be in flight during K-tile 0
   while (true) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (PF2) {   // K-tile 0 landed (K-tile 1's loads and the previous epilogue's stores may remain)
-      if (nk > 1) {
-        if (extra) vm_wait(8 + S_ST);
-        else vm_wait(8);
-      } else if (extra) vm_wait(S_ST);
-      else wait_vmcnt<0>();
-    } else if (extra) vm_wait(S_ST);   // K-tile 0 landed (the previous epilogue's stores may still drain)
+    if (extra) wait_vmcnt<S_ST>();   // K-tile 0 landed (the previous epilogue's stores may still drain)
     else wait_vmcnt<0>();
     // (thread 0) the queue position of the next tile, by inline asm: the compiler would wait for the
     // returned value at once (vmcnt(0), draining the prefetch).  Issued after the wait above and before
@@ -872,13 +826,9 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();
     // one 64-deep K-tile.  MODE 1 (kt == 0): its data was retired by the wait above, so the two
-    // in-tile waits are skipped (they would otherwise also wait for the previous epilogue's stores);
-    // with PF2 it issues nothing (K-tile 1 is in flight) and its Q3 wait leaves the stores in flight.
-    // MODE 2 (PF2, kt == 1): the previous epilogue's S_ST stores sit between K-tile 1's loads and K-tile
-    // 2's, so its Q0 / Q1 waits allow S_ST more; its Q3 wait retires them.
+    // in-tile waits are skipped (they would otherwise also wait for the previous epilogue's stores).
     auto ktile = [&](int kt, auto mode, auto nks) {
       constexpr int MODE = decltype(mode)::value;
-      constexpr bool ISSUE = !(PF2 && MODE == 1);
       const char* sa = smem + (kt & 1) * K_SLOT;
       const char* sb = sa + K_OP;
       const bool nxt = kt + 1 < nk;
@@ -892,84 +842,54 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
         for (int i = 0; i < 4; ++i)
           af[i][ks] = *reinterpret_cast<const bf16x8*>(sa + swz(wr * 128 + i * 16 + fr, ks * 4 + fg));
       }
-      if (ISSUE && nxt) issue(0, kt + 1);
+      if (nxt) issue(0, kt + 1);
       if constexpr (MODE == 0) wait_cnt(2 + (nxt ? 2 : 0));   // B-right(kt) for Q1
-      if constexpr (MODE == 2) {
-        if (nxt) {
-          if (extra) vm_wait(4 + S_ST);
-          else vm_wait(4);
-        } else if (extra) vm_wait(2 + S_ST);
-        else vm_wait(2);
-      }
       sync_mfma(0, bl, 0, nks);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           br[j][ks] = *reinterpret_cast<const bf16x8*>(sb + swz(wc * 64 + 32 + j * 16 + fr, ks * 4 + fg));
-      if (ISSUE && nxt) issue(1, kt + 1);
+      if (nxt) issue(1, kt + 1);
       if constexpr (MODE == 0) wait_cnt(nxt ? 4 : 0);         // A-bot(kt) for Q2
-      if constexpr (MODE == 2) {   // (nk == 2: everything, the tile-queue fetch included, is retired here)
-        if (!nxt) wait_vmcnt<0>();
-        else if (extra) vm_wait(4 + S_ST);
-        else vm_wait(4);
-      }
       sync_mfma(0, br, 1, nks);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           af[i][ks] = *reinterpret_cast<const bf16x8*>(sa + swz(wr * 128 + 64 + i * 16 + fr, ks * 4 + fg));
-      if (ISSUE && nxt) issue(2, kt + 1);
+      if (nxt) issue(2, kt + 1);
       sync_mfma(1, br, 1, nks);
       if (nxt) {
-        if constexpr (ISSUE) {
-          issue(3, kt + 1);
-          wait_cnt(4);   // A-top / B-left(kt+1) for Q0(kt+1); also retires the previous epilogue's stores
-        } else if (extra) {
-          vm_wait(4 + S_ST);   // A-top / B-left(1): B-right / A-bot(1) and the stores may remain
-        } else {
-          vm_wait(4);
-        }
+        issue(3, kt + 1);
+        wait_cnt(4);   // A-top / B-left(kt+1) for Q0(kt+1); also retires the previous epilogue's stores
       }
       sync_mfma(1, bl, 0, nks);
     };
-    if constexpr (PF2) {
-      ktile(0, IC<1>{}, IC<2>{});
-      if (nk > 1) ktile(1, IC<2>{}, IC<2>{});
-      for (int kt = 2; kt < nk; ++kt) ktile(kt, IC<0>{}, IC<2>{});
-    } else {
-      ktile(0, IC<1>{}, IC<2>{});
-      for (int kt = 1; kt < nk; ++kt) ktile(kt, IC<0>{}, IC<2>{});
-    }
+    ktile(0, IC<1>{}, IC<2>{});
+    for (int kt = 1; kt < nk; ++kt) ktile(kt, IC<0>{}, IC<2>{});
     if (wr == 0) __builtin_amdgcn_s_barrier();   // every wave is done reading both ring slots
-    const int cm0 = m0, cn0 = n0, cside = side;
+    const int cm0 = m0, cn0 = n0;
     if (tq) {
       if (tid == 0) {
         asm volatile("" : "+v"(nxt));   // (used only here, after the K loop's waits)
         *s_next = (int)nxt;
-        if ((int)nxt == items - 1) __hip_atomic_store(tq, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((int)nxt == tiles - 1) __hip_atomic_store(tq, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       lds_barrier();
       t = nwg + __builtin_amdgcn_readfirstlane(*s_next);
     } else {
       t += nwg;
     }
-    const bool more = t < items;
+    const bool more = t < tiles;
     if (more) {   // the next tile's first K-tile, ahead of this tile's stores
-      tile = item_tile(t, side);
-      m0 = (tile / gridN) * 256;
-      n0 = (tile % gridN) * 256;
-      set_tile(m0, n0, side);
+      m0 = (t / gridN) * 256;
+      n0 = (t % gridN) * 256;
+      set_tile(m0, n0);
 #pragma unroll
       for (int h = 0; h < 4; ++h) issue(h, 0);
-      if constexpr (PF2) {
-        if (nk > 1)
-#pragma unroll
-          for (int h = 0; h < 4; ++h) issue(h, 1);
-      }
     }
-    epilogue256_buf<STATS>(acc, a, rC, rS, cm0, cn0, wr, wc, fr, fg, HALF ? cside : 0);
+    epilogue256_buf<STATS>(acc, a, rC, rS, cm0, cn0, wr, wc, fr, fg);
     if (!more) break;
     extra = S_ST;
   }
@@ -2205,10 +2125,6 @@ bool nt_4w_ilv() {   // XCP_NT_4W=2: its steps fenced per 8-MFMA group
   const char* e = getenv("XCP_NT_4W");
   return e && e[0] == '2';
 }
-bool nt_pf2() {   // XCP_NT_PF2=1: gemm_nt256p_kernel's two-K-tile prefetch at tile boundaries (read per call; A/B)
-  const char* e = getenv("XCP_NT_PF2");
-  return e && e[0] == '1';
-}
 // The 256p kernel's last K-tile multiplies only its first 32-deep half when the rest of it is past K (the
 // 728-channel flow at its 736 pitch: K = 728 / 736, 24 / 32 of the last 64): 32 of the tile's 768 MFMAs
 // per wave skipped, C and the statistics bitwise equal (the skipped products are +0).  XCP_NT_KHALF=0:
@@ -2216,10 +2132,6 @@ bool nt_pf2() {   // XCP_NT_PF2=1: gemm_nt256p_kernel's two-K-tile prefetch at t
 bool nt_khalf() {
   const char* e = getenv("XCP_NT_KHALF");
   return !(e && e[0] == '0');
-}
-bool nt_half() {   // XCP_NT_HALF=1 (read per call; A/B)
-  const char* e = getenv("XCP_NT_HALF");
-  return e && e[0] == '1';
 }
 
 // XCP_NT_DYNQ=0: the persistent NT kernel walks its static tile list (A/B; read per call)
@@ -2282,15 +2194,10 @@ int xcp_gemm_nt(int dtype, const void* A, long lda, const void* B, long ldb, voi
     // XCP_NT_SPARSE_DGRAD=1 moves their sparse last round to the 128x128 kernel as before)
     const bool queued = tile == 0 && K >= 128 && !stats && nt_dynq();
     const bool partial = tiles > cus && tiles % cus != 0 && (tiles % cus) * 4 < cus * 3;   // last round < 3/4 full
-    // XCP_NT_HALF=1: the last round's tiles as half tiles walked FIRST by the persistent kernel (every row on it;
-    // the half-tile workgroups run half a tile out of step with the rest, so the rounds' epilogue store bursts
-    // are split in two)
-    const bool halves = tile == 0 && persist && partial && K > 64 && nt_half() && !nt_loop2();
-    if ((tile == 0 || tile == 4) && !halves && nt_sparse() && (!queued || nt_sparse_dgrad()) && partial)
+    if ((tile == 0 || tile == 4) && nt_sparse() && (!queued || nt_sparse_dgrad()) && partial)
       mb = (tiles / cus) * cus / gridN;
     NTArgs big = a;
     big.M = min(M, mb * 256);
-    if (halves) big.nsplit = tiles % cus;
     const bool buf = ((long)(big.M - 1) * lda + K) * 2 <= BUF_LIMIT && ((long)(N - 1) * ldb + K) * 2 <= BUF_LIMIT;
     const bool cbuf = ((long)(big.M - 1) * ldc + N) * 2 <= BUF_LIMIT && (!stats || (long)xcp_cdiv(M, 128) * 2 * N * 4 <= BUF_LIMIT);
     if (persist && buf && cbuf) {   // persistent: one workgroup per CU walks the tiles
@@ -2305,11 +2212,6 @@ int xcp_gemm_nt(int dtype, const void* A, long lda, const void* B, long ldb, voi
           hipLaunchKernelGGL(gemm_nt256q_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
         else
           hipLaunchKernelGGL(gemm_nt256q_kernel<false>, dim3(grid), dim3(512), 0, stream, big);
-      } else if (halves) {
-        if (stats)
-          hipLaunchKernelGGL((gemm_nt256p_kernel<true, true, false>), dim3(grid), dim3(512), 0, stream, big);
-        else
-          hipLaunchKernelGGL((gemm_nt256p_kernel<false, true, false>), dim3(grid), dim3(512), 0, stream, big);
       } else if (nt_8w() && K >= 128) {
         if (stats)
           hipLaunchKernelGGL(gemm_nt8w_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
@@ -2325,15 +2227,10 @@ int xcp_gemm_nt(int dtype, const void* A, long lda, const void* B, long ldb, voi
           hipLaunchKernelGGL((gemm_nt4w_kernel<false, true>), dim3(grid), dim3(256), 0, stream, big);
         else
           hipLaunchKernelGGL((gemm_nt4w_kernel<false, false>), dim3(grid), dim3(256), 0, stream, big);
-      } else if (nt_pf2()) {
-        if (stats)
-          hipLaunchKernelGGL((gemm_nt256p_kernel<true, false, true>), dim3(grid), dim3(512), 0, stream, big);
-        else
-          hipLaunchKernelGGL((gemm_nt256p_kernel<false, false, true>), dim3(grid), dim3(512), 0, stream, big);
       } else if (stats)
-        hipLaunchKernelGGL((gemm_nt256p_kernel<true, false, false>), dim3(grid), dim3(512), 0, stream, big);
+        hipLaunchKernelGGL(gemm_nt256p_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
       else
-        hipLaunchKernelGGL((gemm_nt256p_kernel<false, false, false>), dim3(grid), dim3(512), 0, stream, big);
+        hipLaunchKernelGGL(gemm_nt256p_kernel<false>, dim3(grid), dim3(512), 0, stream, big);
     } else if (buf)
       hipLaunchKernelGGL(gemm_nt256k64_kernel<true>, dim3(mb * gridN), dim3(512), 0, stream, big);
     else

@@ -1,5 +1,5 @@
 """A/B of two forms of the persistent 256x256 NT kernel selected by an environment variable the
-library reads per call (e.g. XCP_NT_PF2=0,1: the two-K-tile prefetch at tile boundaries).  For every
+library reads per call (e.g. XCP_NT_KHALF=0,1: the half-deep last K-tile).  For every
 shape: C bitwise equal between the two, BN statistics equal to fp32 rounding, then interleaved timings
 (HIP events, median of rounds).
 
@@ -41,7 +41,7 @@ def timeit(fn, iters=20, warm=3):
 
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    var, vals = (sys.argv[2] if len(sys.argv) > 2 else "XCP_NT_PF2=0,1").split("=")
+    var, vals = (sys.argv[2] if len(sys.argv) > 2 else "XCP_NT_KHALF=0,1").split("=")
     fa, fb = vals.split(",")
     dev = torch.device("cuda:0")
     ops._lib.load()
