@@ -245,6 +245,31 @@ int xcp_opt_adam(const long long* tab, int nchunks, const float* coef, float lr,
 int xcp_opt_adam_dev(const long long* tab, int nchunks, const float* coef, float lr, double b1, double b2, float eps,
                      float wd, const float* tdev, xcp_stream_t stream);
 
+/* ---- the AMP tail of the step (train_au_face.py:678-693): GradScaler + AdamW + AveragedModel ----
+ * The loss scale S (scale / gscale, one fp32) and GradScaler's found_inf (one fp32) are DEVICE
+ * pointers the host never reads; each may be null.  xcp_opt_sumsq_amp: xcp_opt_sumsq over gradients
+ * that still carry S: out[1] = ||g|| / S (what clip_grad_norm_ returns after unscale_), out[0] =
+ * min(1, max_norm / (||g|| / S + 1e-6)) / S (1 / S if max_norm <= 0).  xcp_opt_adam_amp: p *= pmul
+ * first (torch.optim.AdamW: pmul = 1 - lr * weight_decay, wd = 0; L2 decay: pmul = 1), then
+ * xcp_opt_adam's update with g' = g * coef[0], or g / gscale[0] when coef is null; when
+ * found_inf[0] != 0 the launch writes nothing (p, exp_avg, exp_avg_sq stay bit for bit).
+ * xcp_opt_adam_amp_dev: the same with the step count read from tdev[0], as xcp_opt_adam_dev. */
+int xcp_opt_sumsq_amp(const long long* tab, int nchunks, float* part, float max_norm, const float* scale, float* out,
+                      xcp_stream_t stream);
+int xcp_opt_adam_amp(const long long* tab, int nchunks, const float* coef, float lr, float b1, float b2, float eps,
+                     float wd, float pmul, float bc1, float bc2sqrt, const float* gscale, const float* found_inf,
+                     xcp_stream_t stream);
+int xcp_opt_adam_amp_dev(const long long* tab, int nchunks, const float* coef, float lr, double b1, double b2, float eps,
+                         float wd, float pmul, const float* tdev, const float* gscale, const float* found_inf,
+                         xcp_stream_t stream);
+/* torch.optim.swa_utils.AveragedModel.update_parameters in one launch.  tab: DEVICE [nchunks][5] int64
+ * (averaged, source, first element, length <= 16384, plain copy), all fp32; n_averaged: DEVICE int64,
+ * the count before this update (not written).  avg = src on plain-copy rows and while n_averaged ==
+ * 0, else avg = lerp(avg, src, w) with w = 1 / (n_averaged + 1) (decay < 0, the equal running
+ * average) or w = 1 - decay (EMA).  skip: DEVICE fp32 flag or null; non-zero: nothing is written. */
+int xcp_opt_average(const long long* tab, int nchunks, const long long* n_averaged, double decay, const float* skip,
+                    xcp_stream_t stream);
+
 /* njobs permute3 jobs in one launch: jobs = DEVICE array [njobs][12] int64
  * (in, out, d0, d1, d2, p0, p1, p2, out dtype, first workgroup, s0, s1), nblocks workgroups in
  * total; output element (o0, o1, o2) goes to out[o0*s0 + o1*s1 + o2] (strides for the padded

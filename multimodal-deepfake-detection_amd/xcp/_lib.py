@@ -78,6 +78,10 @@ SIGNATURES = {
     "xcp_opt_sumsq": [P, I, P, F, P, P],
     "xcp_opt_adam": [P, I, P, F, F, F, F, F, F, F, P],
     "xcp_opt_adam_dev": [P, I, P, F, D, D, F, F, P, P],
+    "xcp_opt_sumsq_amp": [P, I, P, F, P, P, P],
+    "xcp_opt_adam_amp": [P, I, P, F, F, F, F, F, F, F, F, P, P, P],
+    "xcp_opt_adam_amp_dev": [P, I, P, F, D, D, F, F, F, P, P, P, P],
+    "xcp_opt_average": [P, I, P, D, P, P],
     "xcp_conv3x3_parts": [I, I, I, I],
     "xcp_conv3x3": [I, P, P, P, P, I, I, I, P, P, P],
     "xcp_conv3x3_wgrad_parts": [I, I, I],

@@ -25,6 +25,13 @@ Deviations (both where the script cannot do what it intends under torch 2.x):
   scale); the script reads ``optimizer._step_count``, which torch 2.x optimizers no longer
   carry (it was set by the old LR-scheduler step wrapper), so as written the scheduler and the
   averaged models would never advance.
+
+``fused_optimizer=True`` (GPU models only) runs the tail of the stepping micro-batch on xcp/optim.py
+instead of torch: ``scaler.step(FusedAdamClip(decoupled_weight_decay=True, max_norm=grad_clip,
+capturable=True))`` unscales, clips and applies AdamW in the kernels with GradScaler's scale and
+found_inf left on the device, and the two averaged models are ``FusedAveragedModel``s (one launch
+each).  The scale comparison that gates the scheduler and the averaged models stays, one host read
+per optimiser step.
 """
 import math
 
@@ -61,18 +68,25 @@ def auface_losses(logits_arc, labels, v_tokens, au_tokens, cbfocal, lambda_align
 class AUFaceTrainer:
     def __init__(self, model, samples_per_cls=(1, 1), feat_dim=1024, lr=1e-4, weight_decay=0.01, max_lr=1e-3,
                  epochs=100, steps_per_epoch=1, accum_steps=4, grad_clip=1.0, lambda_align=0.2, lambda_temp=0.1,
-                 use_amp=True, average=True, flat_grads=True, init_scale=2.0 ** 16):
+                 use_amp=True, average=True, flat_grads=True, init_scale=2.0 ** 16, fused_optimizer=False):
         self.model = model
         dev = next(model.parameters()).device
         self.device = dev
+        self.fused_optimizer = fused_optimizer
+        if fused_optimizer and dev.type != "cuda":
+            raise RuntimeError("AUFaceTrainer(fused_optimizer=True) needs the model on the GPU; there is no CPU fallback")
         self.embed_head = nn.Sequential(nn.LazyLinear(256), nn.ReLU(inplace=True), nn.Dropout(0.2),
                                         nn.Linear(256, 128)).to(dev)
         with torch.no_grad():
             self.embed_head(torch.zeros(2, feat_dim, device=dev))   # materialise the LazyLinear
         self.arcface = ArcFaceHead(feat_dim=128, num_classes=2, s=30.0, m=0.30).to(dev)
         self.cbfocal = CBFocalLoss(samples_per_cls=list(samples_per_cls), beta=0.9999, gamma=2.0).to(dev)
-        self.ema_model = AveragedModel(model).to(dev) if average else None
-        self.ema_embed = AveragedModel(self.embed_head).to(dev) if average else None
+        averaged = AveragedModel
+        if fused_optimizer:
+            from .optim import FusedAdamClip, FusedAveragedModel
+            averaged = FusedAveragedModel
+        self.ema_model = averaged(model).to(dev) if average else None
+        self.ema_embed = averaged(self.embed_head).to(dev) if average else None
         self.params = list(model.parameters()) + list(self.embed_head.parameters()) + list(self.arcface.parameters())
         # flat_grads: gradients in one flat fp32 buffer (xcp.ddp.GradBuckets; the backbones add theirs
         # into it directly), all-reduced across ranks on the micro-batch that steps (DDP no_sync)
@@ -80,7 +94,11 @@ class AUFaceTrainer:
         if flat_grads and dev.type == "cuda":
             from .ddp import GradBuckets
             self.buckets = GradBuckets(self.params, module=model)
-        self.optimizer = torch.optim.AdamW(self.params, lr=lr, weight_decay=weight_decay)
+        if fused_optimizer:
+            self.optimizer = FusedAdamClip(self.params, lr=lr, weight_decay=weight_decay, max_norm=grad_clip,
+                                           decoupled_weight_decay=True, capturable=True)
+        else:
+            self.optimizer = torch.optim.AdamW(self.params, lr=lr, weight_decay=weight_decay)
         self.scheduler = torch.optim.lr_scheduler.OneCycleLR(
             self.optimizer, max_lr=max_lr, epochs=epochs,
             steps_per_epoch=max(1, math.ceil(steps_per_epoch / max(1, accum_steps))), pct_start=0.3)
@@ -130,8 +148,9 @@ class AUFaceTrainer:
         if step:
             if self.buckets is not None:
                 self.buckets.allreduce()
-            self.scaler.unscale_(self.optimizer)
-            torch.nn.utils.clip_grad_norm_(self.params, self.grad_clip)
+            if not self.fused_optimizer:   # (the fused optimiser unscales and clips in its kernels)
+                self.scaler.unscale_(self.optimizer)
+                torch.nn.utils.clip_grad_norm_(self.params, self.grad_clip)
             scale = self.scaler.get_scale() if self.scaler.is_enabled() else None
             self.scaler.step(self.optimizer)
             self.scaler.update()

@@ -28,7 +28,33 @@ so that torch Adam's per-parameter semantics hold: a parameter whose state is cr
 unfrozen after epoch 3, train_visual.py:547-556), a parameter whose grad is None on a step while its
 counter-mates step, and a loaded state whose count differs from the others each get a counter of
 their own (one more launch), never the group's count.
+
+``decoupled_weight_decay=True`` (torch.optim.Adam's argument of that name) gives torch.optim.AdamW's
+update: ``p *= 1 - lr * weight_decay`` and no ``weight_decay * p`` term in the gradient
+(xcp_opt_adam_amp / xcp_opt_adam_amp_dev), with or without ``capturable`` and ``max_norm``.
+
+GradScaler on the device: an instance built with ``capturable=True`` sets
+``_step_supports_amp_scaling``, so ``GradScaler.step`` hands it ``grad_scale`` and ``found_inf`` as
+device tensors instead of reading ``found_inf`` back on the host (torch/amp/grad_scaler.py,
+``_maybe_opt_step``).  The kernels multiply each gradient by ``1 / grad_scale`` on load (or by the
+clip coefficient over the unscaled norm, xcp_opt_sumsq_amp; ``param.grad`` keeps the scaled
+gradient) and write nothing when ``found_inf`` is set; no step count advances on such a step, and
+``last_step_skipped`` (a 0-d device tensor, 1.0 after a skipped step) says so without a host read --
+pass it as ``FusedAveragedModel.update_parameters(model, skip=...)``.  So a whole AMP step
+(``scaler.scale(loss).backward(); scaler.step(opt); scaler.update()``) can be captured in a HIP
+graph, overflow steps included.  With ``max_norm``, ``step()`` returns the unscaled pre-clip norm.
+Supported orders: ``scaler.step(opt)`` alone; torch ``clip_grad_norm_`` on the scaled gradients and
+then ``scaler.step(opt)`` (train_visual.py); ``scaler.unscale_(opt)``, a clip, ``scaler.step(opt)``
+(train_au_face.py).  A non-capturable instance keeps its step counts on the host, where a skipped
+step could not be taken back, so it leaves the attribute unset and GradScaler treats it as before.
+Not supported: ``lr`` as a device tensor (a captured step keeps the ``lr`` it was captured with, so
+OneCycleLR inside a graph is not), replacing GradScaler's own non-finite check pass, amsgrad and
+maximize.
+
+``FusedAveragedModel`` is ``torch.optim.swa_utils.AveragedModel`` with ``update_parameters`` as one
+launch (xcp_opt_average) that reads ``n_averaged`` on the device.
 """
+import itertools
 import math
 
 import torch
@@ -41,10 +67,11 @@ CHUNK = 16384
 
 class FusedAdamClip(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None,
-                 capturable=False):
+                 capturable=False, decoupled_weight_decay=False):
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("FusedAdamClip: invalid hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
         for grp in self.param_groups:
             for p in grp["params"]:
                 if p.dtype != torch.float32 or not p.is_contiguous():
@@ -52,6 +79,9 @@ class FusedAdamClip(torch.optim.Optimizer):
                 ops.check_gpu(p)
         self.max_norm = max_norm
         self.capturable = capturable
+        # GradScaler.step attaches grad_scale / found_inf and calls step() with no host read
+        self._step_supports_amp_scaling = bool(capturable)
+        self._skipped = None   # 0-d device flag of the last step, once a found_inf has been seen
         self._counters = {}   # capturable: id(device step counter) -> the counter
         self._tables = {}
         self._out = None
@@ -71,6 +101,22 @@ class FusedAdamClip(torch.optim.Optimizer):
         re-attached gradient can never reuse a table that points at the old storage"""
         return (kind,) + tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
                                for p, g, m, v in rows)
+
+    @staticmethod
+    def _decay(grp):
+        """(wd, pmul) of the update: the L2 coefficient and the factor on p before it.  AdamW's
+        1 - lr * weight_decay is formed in double here, as torch forms it, and passed as a float"""
+        if grp.get("decoupled_weight_decay", False):
+            return 0.0, float(1.0 - grp["lr"] * grp["weight_decay"])
+        return float(grp["weight_decay"]), 1.0
+
+    @property
+    def last_step_skipped(self):
+        """0-d fp32 device tensor: 1.0 if GradScaler's found_inf made the last step() write nothing"""
+        if self._skipped is None:
+            p = self.param_groups[0]["params"][0]
+            self._skipped = torch.zeros((), device=p.device, dtype=torch.float32)
+        return self._skipped
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -133,6 +179,12 @@ class FusedAdamClip(torch.optim.Optimizer):
             for grp, t, rows in launches:
                 tab = self._table(self._key("grp", rows), rows, dev)
                 b1, b2 = grp["betas"]
+                if grp.get("decoupled_weight_decay", False):
+                    wd, pmul = self._decay(grp)
+                    _lib.call("xcp_opt_adam_amp", tab.data_ptr(), tab.shape[0], coef, float(grp["lr"]), float(b1),
+                              float(b2), float(grp["eps"]), wd, pmul, float(1.0 - b1 ** t),
+                              float(math.sqrt(1.0 - b2 ** t)), 0, 0, s)
+                    continue
                 _lib.call("xcp_opt_adam", tab.data_ptr(), tab.shape[0], coef, float(grp["lr"]), float(b1), float(b2),
                           float(grp["eps"]), float(grp["weight_decay"]), float(1.0 - b1 ** t),
                           float(math.sqrt(1.0 - b2 ** t)), s)
@@ -156,6 +208,15 @@ class FusedAdamClip(torch.optim.Optimizer):
         else:
             t = torch.full((), float(value), device=device, dtype=torch.float32)
         self._counters[id(t)] = t
+        return t
+
+    @staticmethod
+    def _amp_flag(t, dev):
+        """GradScaler's scale as one fp32 on the parameters' device (it already is one there)"""
+        if t is None:
+            return None
+        if t.dtype != torch.float32 or t.device != dev:
+            t = t.to(device=dev, dtype=torch.float32)
         return t
 
     def _step_capturable(self, loss):
@@ -213,6 +274,13 @@ class FusedAdamClip(torch.optim.Optimizer):
         if not every:
             return loss
         dev = every[0][0].device
+        # what GradScaler.step attached (grad_scale is None after an explicit scaler.unscale_)
+        gscale, found_inf = self._amp_flag(getattr(self, "grad_scale", None), dev), getattr(self, "found_inf", None)
+        if found_inf is not None:
+            self.last_step_skipped.copy_(found_inf.reshape(()) != 0)
+        elif self._skipped is not None:
+            self._skipped.zero_()
+        skipped = self._skipped if found_inf is not None else None
         with ops.device_guard(every[0][0]):
             s = ops.stream()
             coef = 0
@@ -220,16 +288,148 @@ class FusedAdamClip(torch.optim.Optimizer):
                 tab = self._table(self._key("all", every), every, dev)
                 part = torch.empty(tab.shape[0], device=dev, dtype=torch.float32)
                 self._out = torch.empty(2, device=dev, dtype=torch.float32)
-                _lib.call("xcp_opt_sumsq", tab.data_ptr(), tab.shape[0], part.data_ptr(), float(self.max_norm),
-                          self._out.data_ptr(), s)
+                if gscale is None:
+                    _lib.call("xcp_opt_sumsq", tab.data_ptr(), tab.shape[0], part.data_ptr(), float(self.max_norm),
+                              self._out.data_ptr(), s)
+                else:
+                    _lib.call("xcp_opt_sumsq_amp", tab.data_ptr(), tab.shape[0], part.data_ptr(),
+                              float(self.max_norm), gscale.data_ptr(), self._out.data_ptr(), s)
                 coef = self._out.data_ptr()
             for grp, t, rows in launches:
                 t.add_(1.0)
+                if skipped is not None:
+                    t.sub_(skipped)   # a skipped step is no step: the count advances by 1 - found_inf
                 tab = self._table(self._key("grp", rows), rows, dev)
                 b1, b2 = grp["betas"]
-                _lib.call("xcp_opt_adam_dev", tab.data_ptr(), tab.shape[0], coef, float(grp["lr"]), float(b1), float(b2),
-                          float(grp["eps"]), float(grp["weight_decay"]), t.data_ptr(), s)
+                if gscale is None and skipped is None and not grp.get("decoupled_weight_decay", False):
+                    _lib.call("xcp_opt_adam_dev", tab.data_ptr(), tab.shape[0], coef, float(grp["lr"]), float(b1),
+                              float(b2), float(grp["eps"]), float(grp["weight_decay"]), t.data_ptr(), s)
+                    continue
+                wd, pmul = self._decay(grp)
+                _lib.call("xcp_opt_adam_amp_dev", tab.data_ptr(), tab.shape[0], coef, float(grp["lr"]), float(b1),
+                          float(b2), float(grp["eps"]), wd, pmul, t.data_ptr(),
+                          0 if gscale is None else gscale.data_ptr(), 0 if skipped is None else skipped.data_ptr(), s)
         increment_version([row[0] for row in every])
         if loss is not None:
             return loss
         return self._out[1].clone() if self.max_norm is not None else None
+
+
+class FusedAveragedModel(torch.optim.swa_utils.AveragedModel):
+    """``torch.optim.swa_utils.AveragedModel`` (train_au_face.py:604-605, :690-693) with
+    ``update_parameters`` as one launch over every fp32 parameter (xcp_opt_average): the equal
+    running average (``decay=None``, torch's default) or the exponential one (``decay=d``, what
+    ``multi_avg_fn=get_ema_multi_avg_fn(d)`` computes).  ``n_averaged`` is read by the kernel and
+    advanced on the device, so an update makes no host read.  Same ``state_dict`` as torch's
+    (``n_averaged`` and ``module.``-prefixed keys).  ``avg_fn`` / ``multi_avg_fn`` are not
+    supported, and neither are modules off the GPU: there is no CPU fallback.
+
+    As torch's, with ``use_buffers=False`` the buffers are copied from the model on every update (the
+    fp32 ones as plain-copy rows of the same launch, the others -- BatchNorm's int64
+    ``num_batches_tracked`` -- by torch), and with ``use_buffers=True`` they are averaged with the
+    parameters (the non-fp32 ones by torch ops on the device, in torch's own formula).
+
+    ``update_parameters(model, skip=flag)``: a 0-d device tensor (``FusedAdamClip.last_step_skipped``);
+    non-zero, the call changes nothing, ``n_averaged`` and the buffers included."""
+
+    def __init__(self, model, device=None, avg_fn=None, multi_avg_fn=None, use_buffers=False, decay=None):
+        if avg_fn is not None or multi_avg_fn is not None:
+            raise ValueError("FusedAveragedModel: avg_fn / multi_avg_fn are not supported; decay=None is the equal "
+                             "average and decay=d the exponential one")
+        if decay is not None and not 0.0 <= decay <= 1.0:
+            raise ValueError(f"FusedAveragedModel: invalid decay {decay}")
+        super().__init__(model, device=device, use_buffers=use_buffers)
+        self.decay = decay
+        for t in itertools.chain(self.module.parameters(), self.module.buffers(), model.parameters(), model.buffers()):
+            ops.check_gpu(t)
+        if not self.n_averaged.is_cuda:   # torch leaves it on the CPU unless `device` is given; the kernel reads it
+            self.n_averaged = self.n_averaged.to(next(self.module.parameters()).device)
+        self._tab_key, self._tab, self._own_modules = None, None, None
+
+    @staticmethod
+    def _members(modules):
+        """the parameters and the buffers of a list of modules, in Module.parameters() / .buffers() order
+        (each tensor once), read from the modules' own dicts"""
+        ps, bs, seen = [], [], set()
+        for m in modules:
+            for t in m._parameters.values():
+                if t is not None and id(t) not in seen:
+                    seen.add(id(t))
+                    ps.append(t)
+            for t in m._buffers.values():
+                if t is not None and id(t) not in seen:
+                    seen.add(id(t))
+                    bs.append(t)
+        return ps, bs
+
+    def _pairs(self, model):
+        """(fused rows (avg, src, plain copy), other (avg, src, plain copy)) in torch's pairing"""
+        if self._own_modules is None:   # the averaged copy's module tree never changes; the model's is walked
+            self._own_modules = list(self.module.modules())
+        own_p, own_b = self._members(self._own_modules)
+        src_p, src_b = self._members(model.modules())
+        if len(own_p) != len(src_p) or len(own_b) != len(src_b):
+            raise ValueError("FusedAveragedModel: the model does not match the averaged module")
+        pairs = [(a, b, False) for a, b in zip(own_p, src_p)]
+        pairs += [(a, b, not self.use_buffers) for a, b in zip(own_b, src_b)]
+        fused, other = [], []
+        for a, b, plain in pairs:
+            if a.shape != b.shape:
+                raise ValueError("FusedAveragedModel: the model does not match the averaged module")
+            if a.numel() == 0:
+                continue
+            if a.dtype == torch.float32 and b.dtype == torch.float32:
+                ops.check_gpu(a, b)
+                if not (a.is_contiguous() and b.is_contiguous() and a.device == b.device):
+                    raise ValueError("FusedAveragedModel: fp32 tensors must be contiguous and on one device")
+                fused.append((a, b, plain))
+            else:
+                other.append((a, b, plain))
+        return fused, other
+
+    def _table(self, fused, dev):
+        key = tuple((a.data_ptr(), b.data_ptr(), a.numel(), plain) for a, b, plain in fused)
+        if key != self._tab_key:
+            r = []
+            for a, b, plain in fused:
+                n = a.numel()
+                for s in range(0, n, CHUNK):
+                    r.append([a.data_ptr(), b.data_ptr(), s, min(CHUNK, n - s), int(plain)])
+            self._tab = torch.tensor(r, dtype=torch.int64).to(dev)
+            self._tab_key = key
+        return self._tab
+
+    @torch.no_grad()
+    def update_parameters(self, model, skip=None):
+        fused, other = self._pairs(model)
+        n = self.n_averaged
+        ops.check_gpu(n)
+        if skip is not None:
+            ops.check_gpu(skip)
+            skip = skip.reshape(())
+            if skip.dtype != torch.float32 or skip.device != n.device:
+                skip = skip.to(device=n.device, dtype=torch.float32)
+        if fused:
+            with ops.device_guard(n):
+                tab = self._table(fused, n.device)
+                _lib.call("xcp_opt_average", tab.data_ptr(), tab.shape[0], n.data_ptr(),
+                          -1.0 if self.decay is None else float(self.decay), 0 if skip is None else skip.data_ptr(),
+                          ops.stream())
+        for a, b, plain in other:   # the few non-fp32 tensors (num_batches_tracked): torch ops, no host read
+            b = b.to(a.device)
+            if plain:
+                new = b
+            elif self.decay is None:
+                new = torch.where(n == 0, b, a + (b - a) / (n + 1))
+            else:
+                new = torch.where(n == 0, b, a * self.decay + b * (1 - self.decay))
+            if skip is not None:
+                new = torch.where(skip != 0, a, new.to(a.dtype))
+            a.copy_(new)
+        if skip is None:
+            n.add_(1)
+        else:
+            n.add_((skip == 0).to(n.dtype))
+        # the kernel wrote through raw pointers: bump the version counters as an in-place op would
+        # (the engine repacks its kernel-layout weights by them before the averaged model is evaluated)
+        increment_version([a for a, _, _ in fused])
