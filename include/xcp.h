@@ -136,9 +136,14 @@ int xcp_bn_finalize_part(const float* part, int R, int C, int CP, double count, 
                          float* scale_o, float* shift_o, xcp_stream_t stream);
 /* (dgamma, dbeta may be null.)  flags: XCP_FIN_ACCUMULATE adds to dgamma / dbeta (gradient accumulation into
  * param.grad); XCP_FIN_NARROW reduces with 4-wave instead of 16-wave workgroups, which fit beside a kernel
- * that holds every CU (other summation order: same values to fp64 rounding, not the same bits) */
+ * that holds every CU (other summation order: same values to fp64 rounding, not the same bits);
+ * XCP_FIN_FROZEN: the BatchNorm ran on its running statistics (eval mode; mean / invstd are the ones
+ * xcp_bn_finalize(train = 0) wrote), which are constants of the step: alpha = gamma * invstd and
+ * bcoef = delta = 0, so every consumer of the three coefficients computes dy = gamma * invstd * dz;
+ * dgamma = sum dz * zhat and dbeta = sum dz as in train mode, zhat taken with the running statistics */
 #define XCP_FIN_ACCUMULATE 1
 #define XCP_FIN_NARROW 2
+#define XCP_FIN_FROZEN 4
 int xcp_bn_bwd_finalize_part(const float* part, int R, int C, int CP, double count, const float* gamma,
                              const float* mean, const float* invstd, float* alpha, float* bcoef, float* delta,
                              float* dgamma, float* dbeta, int flags, xcp_stream_t stream);
@@ -191,6 +196,17 @@ int xcp_conv1_wgrad_fused(int dtype, int IH, int IW);
  * when mscale / mshift are given.  Replaces xcp_bn_bwd_apply + xcp_conv1_wgrad on the stored dC1. */
 int xcp_conv1_wgrad_bn(int dtype, const float* X, const void* dZ, const void* Y, const float* alpha, const float* bcoef,
                        const float* delta, const float* mscale, const float* mshift, float* part, int N, int IH, int IW,
+                       xcp_stream_t stream);
+/* conv1 data gradient (the gradient w.r.t. the frames): dX [N][3][IH][IW] fp32 =
+ * sum_{co,ky,kx : ih = 2 oh + ky, iw = 2 ow + kx} dC1[n][oh][ow][co] * W[co][ci][ky][kx], dC1 NHWC (dtype), W the
+ * fp32 [32][3][3][3] kernel, fp32 accumulation, no atomics.  Every element of dX is written: the last row /
+ * column of an even-sized frame, which no window covers, as zero.  Any IH, IW >= 3. */
+int xcp_conv1_dgrad(int dtype, const void* dC1, const float* W, float* dX, int N, int IH, int IW, xcp_stream_t stream);
+/* ... of dC1 = alpha*g + bcoef*Y + delta formed on load and rounded to the storage type (the operands of
+ * xcp_conv1_wgrad_bn; g = dZ masked where Y*mscale + mshift <= 0 when mscale / mshift are given): bitwise
+ * xcp_bn_bwd_apply + xcp_conv1_dgrad on the stored dC1, which is never written.  Both dtypes, every shape. */
+int xcp_conv1_dgrad_bn(int dtype, const void* dZ, const void* Y, const float* W, const float* alpha, const float* bcoef,
+                       const float* delta, const float* mscale, const float* mshift, float* dX, int N, int IH, int IW,
                        xcp_stream_t stream);
 int xcp_permute3(int out_dtype, const float* in, void* out, int d0, int d1, int d2, int p0, int p1, int p2,
                  xcp_stream_t stream);

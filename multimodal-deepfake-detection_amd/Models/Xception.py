@@ -173,9 +173,12 @@ class Xception(nn.Module):
         ops.check_gpu(x)
         eng = self._engine()
         params = [p for _, p in eng.named_params()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return XceptionFunction.apply(eng, self.training, x, *params)
-        feats, _ = eng.forward(x, self.training)
+        # batch statistics or running statistics: what the BatchNorm modules say (model.train() with every
+        # BatchNorm in eval mode is the frozen-statistics fine-tuning recipe), not Xception.training
+        train = eng.bn_training()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            return XceptionFunction.apply(eng, train, x, *params)
+        feats, _ = eng.forward(x, train)
         return feats
 
     def _hooked(self):

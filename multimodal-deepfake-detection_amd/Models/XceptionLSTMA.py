@@ -34,6 +34,10 @@ class XceptionLSTMA(nn.Module):
         if device is not None and not torch.is_tensor(device):
             self.feature_extractor.to(device)
         batch_size, time_steps, c, n_mfcc = audio_batch.shape
+        if torch.is_grad_enabled() and audio_batch.requires_grad:
+            # (the backbone would return a gradient w.r.t. the resized frames, which would stop there, silently)
+            raise NotImplementedError("XceptionLSTMA.extract_features: no gradient w.r.t. the MFCC input "
+                                      "(xcp_resize_bilinear has no backward); detach it or run under torch.no_grad()")
         frames = audio_batch.reshape(batch_size * time_steps, c, n_mfcc, 1)
         frames = ops.resize_bilinear(frames, (64, 64))
         frame_features = self.feature_extractor(frames)

@@ -11,6 +11,7 @@ Layout:
   lstm.py       nn.LSTM drop-in on the fused LSTM kernels
   ddp.py        one-process-per-GPU data parallelism over RCCL
   optim.py      fused clip_grad_norm_ + Adam (a torch.optim.Optimizer)
+  attribution.py  input_gradient: d(score)/d(frames) of a clip model (saliency, FGSM / PGD)
   heads.py      ArcFace head / CB-focal loss on HIP kernels; metrics.py: ROC / EER / pAUC
 
 Precision of the backbone (activations / GEMM operands; accumulation is fp32, master
@@ -55,6 +56,9 @@ def precision(dt):
         yield
     finally:
         set_compute_dtype(prev)
+
+
+from .attribution import input_gradient  # noqa: E402,F401  (d(score)/d(frames) of a clip model)
 
 
 def library_path():

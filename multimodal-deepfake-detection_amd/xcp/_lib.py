@@ -69,6 +69,8 @@ SIGNATURES = {
     "xcp_conv1_wgrad": [I, P, P, P, I, I, I, P],
     "xcp_conv1_wgrad_fused": [I, I, I],
     "xcp_conv1_wgrad_bn": [I, P, P, P, P, P, P, P, P, P, I, I, I, P],
+    "xcp_conv1_dgrad": [I, P, P, P, I, I, I, P],
+    "xcp_conv1_dgrad_bn": [I, P, P, P, P, P, P, P, P, P, I, I, I, P],
     "xcp_permute3": [I, P, P, I, I, I, I, I, I, P],
     "xcp_permute3_blocks": [I, I, I, I, I, I, L, L],
     "xcp_permute3_batch": [P, I, I, P],

@@ -404,7 +404,8 @@ __global__ __launch_bounds__(64 * NWAVES) void bn_bwd_finalize_part_kernel(const
                                                                     int CP, double count, const float* gamma,
                                                                     const float* mean, const float* invstd,
                                                                     float* alpha, float* bcoef, float* delta,
-                                                                    float* dgamma, float* dbeta, int accumulate) {
+                                                                    float* dgamma, float* dbeta, int accumulate,
+                                                                    int frozen) {
   __shared__ double red[NWAVES][64];
   const int c0 = blockIdx.x * FIN_CH;
   double sdz, sdzy;
@@ -419,8 +420,10 @@ __global__ __launch_bounds__(64 * NWAVES) void bn_bwd_finalize_part_kernel(const
   const double a = gm * is;
   const double mdz = sdz / count, mdzy = sdzy / count;
   alpha[c] = (float)a;
-  bcoef[c] = (float)(-a * is * mdzy);
-  delta[c] = (float)(-a * mdz + a * is * mu * mdzy);
+  // frozen (XCP_FIN_FROZEN): mean / invstd are the running statistics, constants of the step, so the
+  // batch-statistics terms drop out and dy = gamma * invstd * dz; dgamma / dbeta keep their form
+  bcoef[c] = frozen ? 0.f : (float)(-a * is * mdzy);
+  delta[c] = frozen ? 0.f : (float)(-a * mdz + a * is * mu * mdzy);
   if (dgamma) {
     dgamma[c] = accumulate ? dgamma[c] + (float)sdzy : (float)sdzy;
     dbeta[c] = accumulate ? dbeta[c] + (float)sdz : (float)sdz;
@@ -1059,14 +1062,15 @@ int xcp_bn_bwd_finalize_part(const float* part, int R, int C, int CP, double cou
                              float* dgamma, float* dbeta, int flags, hipStream_t st) {
   if (C <= 0) return XCP_OK;
   if (R <= 0 || CP < C) return XCP_EINVAL;
-  const int acc = flags & XCP_FIN_ACCUMULATE;
+  const int acc = flags & XCP_FIN_ACCUMULATE, frozen = (flags & XCP_FIN_FROZEN) ? 1 : 0;
   if (flags & XCP_FIN_NARROW)
     hipLaunchKernelGGL(bn_bwd_finalize_part_kernel<FIN_WAVES_NARROW>, dim3((CP + FIN_CH - 1) / FIN_CH),
                        dim3(64 * FIN_WAVES_NARROW), 0, st, part, R, C, CP, count, gamma, mean, invstd, alpha, bcoef,
-                       delta, dgamma, dbeta, acc);
+                       delta, dgamma, dbeta, acc, frozen);
   else
     hipLaunchKernelGGL(bn_bwd_finalize_part_kernel<FIN_WAVES>, dim3((CP + FIN_CH - 1) / FIN_CH), dim3(64 * FIN_WAVES),
-                       0, st, part, R, C, CP, count, gamma, mean, invstd, alpha, bcoef, delta, dgamma, dbeta, acc);
+                       0, st, part, R, C, CP, count, gamma, mean, invstd, alpha, bcoef, delta, dgamma, dbeta, acc,
+                       frozen);
   return (int)hipGetLastError();
 }
 

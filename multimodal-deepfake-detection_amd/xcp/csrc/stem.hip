@@ -1,6 +1,6 @@
-// Entry-flow stem conv1 (3->32, 3x3, stride 2, pad 0, no bias) forward and
-// weight gradient, plus the small permute/cast kernels used to pack fp32
-// master weights into kernel layouts every step.
+// Entry-flow stem conv1 (3->32, 3x3, stride 2, pad 0, no bias) forward, weight
+// gradient and data gradient (the gradient w.r.t. the frames), plus the small
+// permute/cast kernels used to pack fp32 master weights into kernel layouts every step.
 //
 // Reference ops: Xception.conv1 = nn.Conv2d(3, 32, 3, 2, 0, bias=False)
 // (Xception.py:118, called at :168); the input is the NCHW fp32 frame batch
@@ -752,6 +752,232 @@ __global__ __launch_bounds__(256, 3) void conv1_wgrad_row_kernel(const float* __
   }
 }
 
+// ---------------------------------------------------------------------------------
+// conv1 data gradient (the gradient w.r.t. the frames: saliency maps, adversarial inputs):
+//   dX[n,ci,ih,iw] = sum_{co,ky,kx : ih = 2 oh + ky, iw = 2 ow + kx} dC1[n,oh,ow,co] * W[co,ci,ky,kx]
+// dC1 NHWC (T), W the fp32 NCHW parameter, fp32 accumulation, dX fp32 NCHW.  The 2 x 2 input quad
+// (rows 2 j, 2 j + 1; columns 2 i, 2 i + 1) gathers from the four output pixels (j - 1 | j, i - 1 | i):
+//   (even, even) <- (j, i) W[0][0], (j, i-1) W[0][2], (j-1, i) W[2][0], (j-1, i-1) W[2][2]
+//   (even, odd)  <- (j, i) W[0][1], (j-1, i) W[2][1]
+//   (odd,  even) <- (j, i) W[1][0], (j, i-1) W[1][2]
+//   (odd,  odd)  <- (j, i) W[1][1]
+// 27 FMAs per output channel and quad; output pixels outside the frame count as zero, so the last row /
+// column of an even-sized frame (covered by no window) comes out zero from the same code: no memset.
+//
+// MODE 1 / 2: dC1 is formed on load from dZ and Y, dC1 = T(alpha * g + bcoef * Y + delta), g = dZ masked
+// to 0 where Y * ms + mt <= 0 (MODE 2) -- the value bn_bwd_apply_kernel stores (same fma order, same
+// rounding); everything after the load is the MODE 0 code, so the fused form equals xcp_bn_bwd_apply +
+// the plain kernel bit for bit.  No atomics: one thread owns an input quad, the sums run in a fixed order.
+template <typename T, int MODE>
+XCP_DEV float dgrad_form(float d, float y, float al, float bc, float de, float sm, float tm) {
+  if constexpr (MODE == 2) d = fmaf(y, sm, tm) > 0.f ? d : 0.f;
+  if constexpr (MODE != 0) d = rnd<T>(fmaf(al, d, fmaf(bc, y, de)));
+  return d;
+}
+
+constexpr int D1_RPC = 16;                // row pairs a workgroup walks (it re-reads one output row per chunk)
+constexpr int D1_MAXOW = 225;             // LDS form: two staged rows of (OW + 2) pixels at the fp32 pitch <= 64 KB
+template <typename T> struct D1Pitch {    // bytes per staged pixel: 32 channels + 16 B (16-B staging stores stay aligned;
+  static constexpr int v = C1 * (int)sizeof(T) + 16;   // consecutive pixels start 20 / 36 banks apart instead of 16 / 32:
+};                                        // the compute loop's 4-B / 8-B reads of 64 consecutive pixels are 4- / 2-way
+                                          // bank conflicts instead of 16-way; an odd dword pitch would need 4-B staging)
+
+// 27 FMAs of one output channel: g = dC1 at (j, i), (j, i-1), (j-1, i), (j-1, i-1); w = W[co] ([ci][ky][kx])
+XCP_DEV void load2(const float* p, float* v) {
+  const float2 q = *reinterpret_cast<const float2*>(p);
+  v[0] = q.x;
+  v[1] = q.y;
+}
+XCP_DEV void load2(const bf16* p, float* v) {
+  const unsigned q = *reinterpret_cast<const unsigned*>(p);
+  v[0] = __uint_as_float(q << 16);
+  v[1] = __uint_as_float(q & 0xffff0000u);
+}
+
+XCP_DEV void dgrad_fma(float (&acc)[3][4], const float* __restrict__ w, float g11, float g10, float g01, float g00) {
+#pragma unroll
+  for (int ci = 0; ci < 3; ++ci) {
+    const float* k = w + ci * 9;
+    acc[ci][0] = fmaf(g11, k[0], fmaf(g10, k[2], fmaf(g01, k[6], fmaf(g00, k[8], acc[ci][0]))));
+    acc[ci][1] = fmaf(g11, k[1], fmaf(g01, k[7], acc[ci][1]));
+    acc[ci][2] = fmaf(g11, k[3], fmaf(g10, k[5], acc[ci][2]));
+    acc[ci][3] = fmaf(g11, k[4], acc[ci][3]);
+  }
+}
+
+typedef float f2a4 __attribute__((ext_vector_type(2), aligned(4)));   // (frame rows: 4-B aligned only)
+
+// A workgroup walks D1_RPC consecutive row pairs j of one frame.  Output row j is staged in LDS buffer
+// j & 1 (row j - 1 stays in the other from the step before), pixels at slots 1 .. OW between two zero
+// slots; a row outside the frame is a zero buffer.  Thread i owns quad i of the row pair: per pair of channels
+// four 4-B (bf16; fp32: 8-B) LDS reads, the kernel through the scalar cache (uniform addresses).
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void conv1_dgrad_row_kernel(const T* __restrict__ dZ, const T* __restrict__ Yv,
+                                                              const float* __restrict__ Wt, const float* alpha,
+                                                              const float* bcoef, const float* delta, const float* ms,
+                                                              const float* mt, float* __restrict__ dX, int N, int IH,
+                                                              int IW, int OH, int OW, int nchunk) {
+  extern __shared__ __attribute__((aligned(16))) char sg[];   // [2][OW + 2] pixels of D1Pitch bytes
+  constexpr int PB = D1Pitch<T>::v, CPP = C1 * (int)sizeof(T) / 16, EPC = 16 / (int)sizeof(T);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int n = blockIdx.x / nchunk, ch = blockIdx.x - n * nchunk;
+  const int NJ = (IH + 1) / 2, NQ = (IW + 1) / 2;
+  const int j0 = ch * D1_RPC, j1 = min(j0 + D1_RPC, NJ);
+  const int rowb = (OW + 2) * PB;
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+  // stage output row oh (zeros when it lies outside the frame) into buffer b, pixel slots 1 .. OW
+  auto stage = [&](int oh, int b) {
+    char* dst = sg + b * rowb + PB;
+    const int nchk = OW * CPP;
+    if (oh < 0 || oh >= OH) {
+      for (int c = tid; c < nchk; c += nt) {
+        const int p = c / CPP, q = c - p * CPP;
+        *reinterpret_cast<u32x4*>(dst + p * PB + q * 16) = u32x4{0u, 0u, 0u, 0u};
+      }
+      return;
+    }
+    const long base = ((long)n * OH + oh) * OW * C1;
+    for (int c = tid; c < nchk; c += nt) {
+      const int p = c / CPP, q = c - p * CPP;
+      if constexpr (MODE == 0) {
+        *reinterpret_cast<u32x4*>(dst + p * PB + q * 16) = *reinterpret_cast<const u32x4*>(dZ + base + (long)c * EPC);
+      } else {
+        float d[EPC], y[EPC], al[EPC], bc[EPC], de[EPC], sm[EPC], tm[EPC];
+        VecIO<T, EPC>::load(dZ + base + (long)c * EPC, d);
+        VecIO<T, EPC>::load(Yv + base + (long)c * EPC, y);
+        VecIO<float, EPC>::load(alpha + q * EPC, al);
+        VecIO<float, EPC>::load(bcoef + q * EPC, bc);
+        VecIO<float, EPC>::load(delta + q * EPC, de);
+        if constexpr (MODE == 2) {
+          VecIO<float, EPC>::load(ms + q * EPC, sm);
+          VecIO<float, EPC>::load(mt + q * EPC, tm);
+        }
+#pragma unroll
+        for (int e = 0; e < EPC; ++e)
+          d[e] = dgrad_form<T, MODE>(d[e], y[e], al[e], bc[e], de[e], MODE == 2 ? sm[e] : 0.f, MODE == 2 ? tm[e] : 0.f);
+        VecIO<T, EPC>::store(reinterpret_cast<T*>(dst + p * PB + q * 16), d);
+      }
+    }
+  };
+
+  // the zero slots (ow = -1 and ow = OW) of both buffers
+  for (int c = tid; c < 4 * CPP; c += nt) {
+    const int s = c / CPP, q = c - s * CPP;
+    *reinterpret_cast<u32x4*>(sg + (s >> 1) * rowb + ((s & 1) ? (OW + 1) * PB : 0) + q * 16) = u32x4{0u, 0u, 0u, 0u};
+  }
+  stage(j0 - 1, (j0 + 1) & 1);
+  for (int j = j0; j < j1; ++j) {
+    stage(j, j & 1);
+    __syncthreads();
+    const char* r1 = sg + (j & 1) * rowb;         // output row j
+    const char* r0 = sg + ((j + 1) & 1) * rowb;   // output row j - 1
+    for (int i = tid; i < NQ; i += nt) {
+      float acc[3][4];
+#pragma unroll
+      for (int ci = 0; ci < 3; ++ci)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[ci][e] = 0.f;
+      // slot i holds ow = i - 1, slot i + 1 holds ow = i.  Two channels per pass of a loop that is NOT unrolled:
+      // their 54 weights come through the scalar cache into SGPRs.  Unrolled (in part or whole), hipcc fetches
+      // every weight of the unrolled body first -- 216 per eight channels -- and spills SGPRs to VGPR lanes
+      // (308 v_readlane / v_writelane per eight channels, 629 us at 256 x 299^2), and holds up to 128 gradient
+      // values (226 VGPRs, two waves per SIMD).
+#pragma unroll 1
+      for (int c2 = 0; c2 < C1; c2 += 2) {
+        float g11[2], g10[2], g01[2], g00[2];
+        const int co = c2 * (int)sizeof(T);
+        load2(reinterpret_cast<const T*>(r1 + (i + 1) * PB + co), g11);
+        load2(reinterpret_cast<const T*>(r1 + i * PB + co), g10);
+        load2(reinterpret_cast<const T*>(r0 + (i + 1) * PB + co), g01);
+        load2(reinterpret_cast<const T*>(r0 + i * PB + co), g00);
+        dgrad_fma(acc, Wt + c2 * K1, g11[0], g10[0], g01[0], g00[0]);
+        dgrad_fma(acc, Wt + (c2 + 1) * K1, g11[1], g10[1], g01[1], g00[1]);
+      }
+      const bool c1ok = 2 * i + 1 < IW;
+#pragma unroll
+      for (int ci = 0; ci < 3; ++ci) {
+        float* o = dX + (((long)n * 3 + ci) * IH + 2 * j) * IW + 2 * i;
+        if (c1ok) *reinterpret_cast<f2a4*>(o) = f2a4{acc[ci][0], acc[ci][1]};
+        else o[0] = acc[ci][0];
+        if (2 * j + 1 < IH) {
+          if (c1ok) *reinterpret_cast<f2a4*>(o + IW) = f2a4{acc[ci][2], acc[ci][3]};
+          else o[IW] = acc[ci][2];
+        }
+      }
+    }
+    __syncthreads();   // row j - 1's buffer is free for row j + 1
+  }
+}
+
+// Frames too wide for the staged rows: one thread per input pixel, dC1 read (and formed) straight from
+// global memory, taps by the pixel's parity.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void conv1_dgrad_kernel(const T* __restrict__ dZ, const T* __restrict__ Yv,
+                                                          const float* __restrict__ Wt, const float* alpha,
+                                                          const float* bcoef, const float* delta, const float* ms,
+                                                          const float* mt, float* __restrict__ dX, int N, int IH, int IW,
+                                                          int OH, int OW) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)N * IH * IW) return;
+  const int iw = (int)(g % IW);
+  const long t = g / IW;
+  const int ih = (int)(t % IH), n = (int)(t / IH);
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int ky = ih & 1; ky < 3; ky += 2) {
+    const int oh = (ih - ky) / 2;
+    if (ih < ky || oh >= OH) continue;
+    for (int kx = iw & 1; kx < 3; kx += 2) {
+      const int ow = (iw - kx) / 2;
+      if (iw < kx || ow >= OW) continue;
+      const long o = (((long)n * OH + oh) * OW + ow) * C1;
+      for (int c8 = 0; c8 < C1; c8 += 8) {
+        float d[8];
+        VecIO<T, 8>::load(dZ + o + c8, d);
+        if constexpr (MODE != 0) {
+          float y[8];
+          VecIO<T, 8>::load(Yv + o + c8, y);
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            d[e] = dgrad_form<T, MODE>(d[e], y[e], alpha[c8 + e], bcoef[c8 + e], delta[c8 + e], MODE == 2 ? ms[c8 + e] : 0.f,
+                                       MODE == 2 ? mt[c8 + e] : 0.f);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float* w = Wt + (c8 + e) * K1 + ky * 3 + kx;
+          acc[0] = fmaf(d[e], w[0], acc[0]);
+          acc[1] = fmaf(d[e], w[9], acc[1]);
+          acc[2] = fmaf(d[e], w[18], acc[2]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int ci = 0; ci < 3; ++ci) dX[(((long)n * 3 + ci) * IH + ih) * IW + iw] = acc[ci];
+}
+
+template <typename T, int MODE>
+int conv1_dgrad_launch(const void* dZ, const void* Y, const float* W, const float* alpha, const float* bcoef,
+                       const float* delta, const float* ms, const float* mt, float* dX, int N, int IH, int IW,
+                       hipStream_t st) {
+  const int OH = (IH - 3) / 2 + 1, OW = (IW - 3) / 2 + 1;
+  if (OW <= D1_MAXOW) {
+    const int NJ = (IH + 1) / 2, NQ = (IW + 1) / 2, nchunk = (NJ + D1_RPC - 1) / D1_RPC;
+    const long blocks = (long)N * nchunk;
+    if (blocks > 0x7fffffffL) return XCP_EUNSUPPORTED;
+    const int nt = NQ >= 256 ? 256 : ((NQ + 63) / 64) * 64;
+    const size_t lds = (size_t)2 * (OW + 2) * D1Pitch<T>::v;
+    hipLaunchKernelGGL((conv1_dgrad_row_kernel<T, MODE>), dim3((unsigned)blocks), dim3(nt), lds, st, (const T*)dZ,
+                       (const T*)Y, W, alpha, bcoef, delta, ms, mt, dX, N, IH, IW, OH, OW, nchunk);
+  } else {
+    const long blocks = ((long)N * IH * IW + 255) / 256;
+    if (blocks > 0x7fffffffL) return XCP_EUNSUPPORTED;
+    hipLaunchKernelGGL((conv1_dgrad_kernel<T, MODE>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)dZ, (const T*)Y,
+                       W, alpha, bcoef, delta, ms, mt, dX, N, IH, IW, OH, OW);
+  }
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
 namespace {
@@ -912,6 +1138,35 @@ int xcp_conv1_wgrad_bn(int dtype, const float* X, const void* dZ, const void* Y,
     hipLaunchKernelGGL(conv1_wgrad_row_kernel<1>, dim3(blocks), dim3(256), 0, st, X, (const bf16*)dZ, (const bf16*)Y,
                        alpha, bcoef, delta, nullptr, nullptr, part, N, IH, IW, OH, OW);
   return (int)hipGetLastError();
+}
+
+// conv1 data gradient: dX [N][3][IH][IW] fp32 (every element written, the uncovered last row / column of an
+// even-sized frame as zero) from dC1 [N][OH][OW][32] (dtype) and the fp32 [32][3][3][3] kernel; any IH, IW >= 3
+int xcp_conv1_dgrad(int dtype, const void* dC1, const float* W, float* dX, int N, int IH, int IW, hipStream_t st) {
+  if (IH < 3 || IW < 3 || N < 0) return XCP_EINVAL;
+  if (N == 0) return XCP_OK;
+  if (dtype == XCP_BF16)
+    return conv1_dgrad_launch<bf16, 0>(dC1, nullptr, W, nullptr, nullptr, nullptr, nullptr, nullptr, dX, N, IH, IW, st);
+  if (dtype == XCP_F32)
+    return conv1_dgrad_launch<float, 0>(dC1, nullptr, W, nullptr, nullptr, nullptr, nullptr, nullptr, dX, N, IH, IW, st);
+  return XCP_EUNSUPPORTED;
+}
+
+// ... with BN1's backward apply (and the ReLU mask when mscale / mshift are given) formed on load, the operands
+// of xcp_conv1_wgrad_bn: bitwise xcp_bn_bwd_apply + xcp_conv1_dgrad on the stored dC1, which is never written
+int xcp_conv1_dgrad_bn(int dtype, const void* dZ, const void* Y, const float* W, const float* alpha, const float* bcoef,
+                       const float* delta, const float* mscale, const float* mshift, float* dX, int N, int IH, int IW,
+                       hipStream_t st) {
+  if (IH < 3 || IW < 3 || N < 0) return XCP_EINVAL;
+  if ((mscale == nullptr) != (mshift == nullptr)) return XCP_EINVAL;
+  if (N == 0) return XCP_OK;
+#define XCP_D1(TT)                                                                                               \
+  (mscale ? conv1_dgrad_launch<TT, 2>(dZ, Y, W, alpha, bcoef, delta, mscale, mshift, dX, N, IH, IW, st)          \
+          : conv1_dgrad_launch<TT, 1>(dZ, Y, W, alpha, bcoef, delta, nullptr, nullptr, dX, N, IH, IW, st))
+  if (dtype == XCP_BF16) return XCP_D1(bf16);
+  if (dtype == XCP_F32) return XCP_D1(float);
+#undef XCP_D1
+  return XCP_EUNSUPPORTED;
 }
 
 // conv1 forward (bf16 output) with BN1's batch-statistics partials part[xcp_conv1_fwd_parts][2][32]

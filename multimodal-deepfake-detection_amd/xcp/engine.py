@@ -198,7 +198,8 @@ class XceptionEngine:
             raise NotImplementedError("xcp engine: Xception stem conv1 must be 3->32 3x3 s2 p0")
         if (c2.in_channels, c2.out_channels, c2.kernel_size, c2.stride, c2.padding) != (32, 64, (3, 3), (1, 1), (0, 0)):
             raise NotImplementedError("xcp engine: Xception stem conv2 must be 32->64 3x3 s1 p0")
-        self.bn_modules = [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
+        self.bn_named = [(n, m) for n, m in model.named_modules() if isinstance(m, nn.BatchNorm2d)]
+        self.bn_modules = [m for _, m in self.bn_named]
         self._pack_key = None
         self._packed = {}
         self._packed_bwd_key = None
@@ -219,6 +220,19 @@ class XceptionEngine:
             prio = torch.cuda.Stream.priority_range()[0] if SIDE_PRIO_LOW else 0
             st = self._side = torch.cuda.Stream(dev, priority=prio)
         return st
+
+    def bn_training(self):
+        """The engine's ``train`` flag: the common ``.training`` of the backbone's BatchNorm modules (True:
+        batch statistics, running buffers updated; False: running statistics, buffers untouched).  The
+        backbone has no other mode-dependent module, so ``model.train()`` with every BatchNorm in eval mode
+        -- fine-tuning on frozen statistics -- runs exactly as ``model.eval()`` does."""
+        on = [n for n, m in self.bn_named if m.training]
+        if on and len(on) != len(self.bn_named):
+            off = [n for n, m in self.bn_named if not m.training]
+            raise NotImplementedError(
+                "xcp engine: the backbone's BatchNorm modules must all be in train mode or all in eval mode; "
+                f"in train mode: {', '.join(on)}; in eval mode: {', '.join(off)}")
+        return bool(on)
 
     # ------------------------------------------------------------ parameters
     def named_params(self):
@@ -345,14 +359,15 @@ class XceptionEngine:
         return Y, st
 
     # ------------------------------------------------------------ forward
-    def forward(self, x, train):
-        """x: [N,3,H,W] fp32 (NCHW, as XceptionLSTMV.extract_features feeds it).
+    def forward(self, x, train, for_backward=False):
+        """x: [N,3,H,W] fp32 (NCHW, as XceptionLSTMV.extract_features feeds it).  train: batch-statistics
+        BatchNorm (False: running statistics); for_backward: ``backward`` may follow (XceptionFunction).
         Returns (features [N,2048] fp32, saved-state dict for backward)."""
         ops.check_gpu(x)
         with ops.device_guard(x):
-            return self._forward(x, train)
+            return self._forward(x, train, for_backward)
 
-    def _forward(self, x, train):
+    def _forward(self, x, train, for_backward=False):
         self.device = x.device
         x = x.contiguous().float()
         N, C0, IH, IW = x.shape
@@ -380,7 +395,7 @@ class XceptionEngine:
         R2 = ops.conv3x3_parts(0, N, OH1, OW1) if self.dtype == torch.bfloat16 else 0
         # conv2 and its weight gradient apply BN1 + ReLU to conv1's output as they stage it: a1 =
         # relu(bn1(c1)) is never written (CONV2_ACT_ON_LOAD)
-        act_on_load = CONV2_ACT_ON_LOAD and R2 > 0 and (not train or ops.conv3x3_wgrad_parts(N, OH1, OW1) > 0)
+        act_on_load = CONV2_ACT_ON_LOAD and R2 > 0 and (not (train or for_backward) or ops.conv3x3_wgrad_parts(N, OH1, OW1) > 0)
         if act_on_load:
             a1 = None
         else:
@@ -485,20 +500,23 @@ class XceptionEngine:
         return out, OH, OW, bs
 
     # ------------------------------------------------------------ backward
-    def backward(self, S, dfeat, out=None, notify=None):
-        """dfeat [N,2048] fp32 -> backbone parameter gradients.
+    INPUT = "<frames>"   # key of the input gradient in backward's result
+
+    def backward(self, S, dfeat, out=None, notify=None, need=None, input_grad=False):
+        """dfeat [N,2048] fp32 -> backbone parameter gradients, after a forward in either mode (train=False:
+        the BatchNorms ran on their running statistics, which are constants of the step -- XCP_FIN_FROZEN).
 
         out None: returns {param name: fresh fp32 gradient}.  out {name: tensor}: the
         gradients of those parameters are ADDED to the given tensors (param.grad views);
         others are returned fresh.  notify(names, side_stream): called after the kernels
         that produce the gradients of ``names`` are enqueued (side_stream: the stream the
-        weight gradients run on, or None)."""
-        if not S["train"]:
-            raise RuntimeError("xcp engine backward needs a train-mode forward (batch-stat BatchNorm)")
+        weight gradients run on, or None).  need (a set of parameter names; None: all): the others'
+        stand-alone weight-gradient launches and slab reductions are skipped.  input_grad: also the
+        gradient w.r.t. the frames, fp32 [N,3,IH,IW], under the key ``XceptionEngine.INPUT``."""
         with ops.device_guard(dfeat):
-            return self._backward(S, dfeat, out, notify)
+            return self._backward(S, dfeat, out, notify, need, input_grad)
 
-    def _backward(self, S, dfeat, out, notify):
+    def _backward(self, S, dfeat, out, notify, need=None, input_grad=False):
         pk = self.pack_bwd()
         m = self.model
         N = S["N"]
@@ -507,6 +525,10 @@ class XceptionEngine:
         dfeat = dfeat.contiguous().float()
         out = out or {}
         pending = []
+        frozen = not S["train"]
+
+        def needed(name):
+            return need is None or name in need
 
         def g(name, shape):
             """(gradient tensor of parameter ``name``, accumulate into it?)"""
@@ -539,6 +561,8 @@ class XceptionEngine:
 
         def wgrad(G, X, M, Nn, K, name, shape, defer=False, **kw):
             """dW[Nn][K] = G^T X (logical channels; G / X at their channel pitches)"""
+            if not needed(name):
+                return
             kw.setdefault("ldg", pc(Nn))
             kw.setdefault("ldx", pc(K))
             dst, acc = g(name, shape)
@@ -582,12 +606,16 @@ class XceptionEngine:
             """BN backward up to its coefficients (alpha, bcoef, delta; at the channel pitch);
             writes the affine grads"""
             P = part[1] if part is not None else 0
-            (gw, acc), (gb, acc_b) = g(name + ".weight", (C,)), g(name + ".bias", (C,))
-            if acc != acc_b:
-                raise NotImplementedError(f"xcp engine: {name}.weight and .bias must both (or neither) require grad")
+            if needed(name + ".weight") or needed(name + ".bias"):
+                (gw, acc), (gb, acc_b) = g(name + ".weight", (C,)), g(name + ".bias", (C,))
+                if acc != acc_b:
+                    raise NotImplementedError(f"xcp engine: {name}.weight and .bias must both (or neither) require grad")
+            else:
+                gw = gb = None
+                acc = False
             return ops.bn_backward_coef(dZ, Y, rows, C, _bn_ref(bnmod), st, gw, gb,
                                         part=part[0] if part is not None else None, R=P, relu=relu, accumulate=acc,
-                                        CP=pc(C), narrow=narrow)
+                                        CP=pc(C), narrow=narrow, frozen=frozen)
 
         def bn_bwd(bnmod, name, dZ, Y, rows, C, st, part=None, relu=False):
             coef = bn_coef(bnmod, name, dZ, Y, rows, C, st, part, relu)
@@ -607,7 +635,9 @@ class XceptionEngine:
             if FUSED_UNIT_BWD and ops.unit_bwd_rows_per_split(dZ.dtype, M, u.cout, u.cin) > 0:
                 # narrow units: BN apply + pointwise dgrad + wgrad in one pass (dY stays on chip)
                 coef = bn_coef(u.bn, u.bn_name, dZ, rec["y"], M, u.cout, rec["st"], part)
-                dst, acc = g(u.name + ".pointwise.weight", (u.cout, u.cin, 1, 1))
+                # (a frozen weight: the kernel's by-product slabs are left unreduced)
+                dst, acc = g(u.name + ".pointwise.weight", (u.cout, u.cin, 1, 1)) \
+                    if needed(u.name + ".pointwise.weight") else (None, False)
                 ops.unit_bwd(dZ, rec["y"], coef, pk[u.name + ".pwT"], rec["d"], dD, M, u.cout, u.cin, dst, acc)
             else:
                 dY = bn_bwd(u.bn, u.bn_name, dZ, rec["y"], M, u.cout, rec["st"], part)
@@ -618,7 +648,7 @@ class XceptionEngine:
                     wgrad(dY, rec["d"], M, u.cout, u.cin, u.name + ".pointwise.weight", (u.cout, u.cin, 1, 1),
                           defer=WGRAD_DEFER)
             dX = self._empty(M * pc(u.cin))
-            dwg, acc = g(u.name + ".conv1.weight", (u.cin, 1, 3, 3))
+            dwg, acc = g(u.name + ".conv1.weight", (u.cin, 1, 3, 3)) if needed(u.name + ".conv1.weight") else (None, False)
             bnp = ops.dw_bwd(rec["act"], dD, rec["src"], pk[u.name + ".dw"], rec["sc"], rec["sh"], dX, dwg, N, H, W,
                              pc(u.cin), dRes=dRes, dSkip=dSkip, skip_geom=skip_geom,
                              bn_stats=res_bn[1] if res_bn is not None else prev_st, accumulate=acc,
@@ -652,6 +682,8 @@ class XceptionEngine:
             dC2 = bn_bwd(m.bn2, "bn2", dX, S["c2"], rows2, 64, S["s2"], relu=True)   # relu (Xception.py:174) fused
         def conv2_wgrad(st2):
             """conv2's weight gradient (from dC2 and a1) on stream st2 (None: the current one)"""
+            if not needed("conv2.weight"):
+                return
             if st2 is not None:
                 st2.wait_stream(main)
             c2g, acc = g("conv2.weight", (64, 32, 3, 3))   # (allocated on the main stream)
@@ -693,14 +725,30 @@ class XceptionEngine:
             conv2_wgrad(st2)
         if not STEM_BN1_FIRST:
             coef1 = bn_coef(m.bn1, "bn1", dA1, S["c1"], rows1, 32, S["s1"], None, True)
-        c1g, acc = g("conv1.weight", (32, 3, 3, 3))
-        if CONV1_BN_FUSED and pc(32) == 32 and ops.conv1_wgrad_fused(self.dtype, S["IH"], S["IW"]):
-            ops.conv1_wgrad_bn(S["x"], dA1, S["c1"], coef1, S["s1"], c1g, N, S["IH"], S["IW"], 32, relu=True,
-                               accumulate=acc)
-        else:
+        # conv1's weight gradient and (input_grad) its data gradient, the gradient w.r.t. the frames: both form
+        # BN1's backward apply + ReLU mask on load where the fused weight gradient takes the shape (dC1 is
+        # never stored), and both read one stored dC1 otherwise
+        need_w1 = needed("conv1.weight")
+        fused1 = CONV1_BN_FUSED and pc(32) == 32 and ops.conv1_wgrad_fused(self.dtype, S["IH"], S["IW"])
+        dC1 = None
+        if not fused1 and (need_w1 or input_grad):
             dC1 = self._empty(rows1 * pc(32))
             ops.bn_apply_coef(dA1, S["c1"], dC1, coef1, S["s1"], rows1, pc(32), relu=True)
-            ops.conv1_wgrad(S["x"], dC1, c1g, N, S["IH"], S["IW"], accumulate=acc)
+        if need_w1:
+            c1g, acc = g("conv1.weight", (32, 3, 3, 3))
+            if fused1:
+                ops.conv1_wgrad_bn(S["x"], dA1, S["c1"], coef1, S["s1"], c1g, N, S["IH"], S["IW"], 32, relu=True,
+                                   accumulate=acc)
+            else:
+                ops.conv1_wgrad(S["x"], dC1, c1g, N, S["IH"], S["IW"], accumulate=acc)
+        if input_grad:
+            dx = torch.empty((N, 3, S["IH"], S["IW"]), device=dev, dtype=torch.float32)
+            w1 = m.conv1.weight.detach()
+            if fused1:
+                ops.conv1_dgrad_bn(dA1, S["c1"], w1, coef1, S["s1"], dx, N, S["IH"], S["IW"], 32, relu=True)
+            else:
+                ops.conv1_dgrad(dC1, w1, dx, N, S["IH"], S["IW"])
+            grads[self.INPUT] = dx
         if side is not None:
             main.wait_stream(side)
         keep.clear()   # after the wait: reuse of these blocks is ordered behind the side stream
@@ -769,13 +817,15 @@ class XceptionEngine:
 
 class XceptionFunction(torch.autograd.Function):
     """Autograd node for the whole backbone: inputs (frames, *backbone params),
-    output features [N,2048].  Gradients w.r.t. the frames are not produced (the
-    reference never differentiates w.r.t. its input clips)."""
+    output features [N,2048].  The gradient w.r.t. the frames (saliency maps, adversarial inputs) is
+    produced when they require one, in their dtype and shape; parameters that do not require grad cost no
+    stand-alone weight-gradient launch.  No double backward."""
 
     @staticmethod
     def forward(ctx, engine, train, x, *params):
-        feats, S = engine.forward(x, train)
+        feats, S = engine.forward(x, train, for_backward=True)
         ctx.engine, ctx.S = engine, S
+        ctx.x_needs, ctx.x_dtype, ctx.x_shape = ctx.needs_input_grad[2], x.dtype, x.shape
         ctx.names = [n for n, _ in engine.named_params()]
         ctx.needs = [p.requires_grad for p in params]
         ctx.params = params
@@ -788,9 +838,9 @@ class XceptionFunction(torch.autograd.Function):
         need = {n for n, nd in zip(ctx.names, ctx.needs) if nd}
         if sink is None:
             # default: hand the gradients to autograd (hooks and autograd.grad behave as usual)
-            grads = eng.backward(ctx.S, dfeat)
+            grads = eng.backward(ctx.S, dfeat, need=need, input_grad=ctx.x_needs)
             ctx.S = ctx.params = None
-            return (None, None, None, *[grads.get(n) if n in need else None for n in ctx.names])
+            return (None, None, _dx(ctx, grads), *[grads.get(n) if n in need else None for n in ctx.names])
         # gradient sink: accumulate straight into the sink's param.grad views, block by block
         out = {}
         for n, p in zip(ctx.names, ctx.params):
@@ -799,7 +849,13 @@ class XceptionFunction(torch.autograd.Function):
                 # None), so what the kernels add is what the bucket all-reduce sees
                 out[n] = sink.grad_view(p)
         by_name = dict(zip(ctx.names, ctx.params))
-        eng.backward(ctx.S, dfeat, out=out,
-                     notify=lambda names, side: sink.ready([by_name[n] for n in names if n in need], side))
+        grads = eng.backward(ctx.S, dfeat, out=out, need=need, input_grad=ctx.x_needs,
+                             notify=lambda names, side: sink.ready([by_name[n] for n in names if n in need], side))
         ctx.S = ctx.params = None
-        return (None, None, None, *([None] * len(ctx.names)))
+        return (None, None, _dx(ctx, grads), *([None] * len(ctx.names)))
+
+
+def _dx(ctx, grads):
+    """the frames' gradient in the frames' dtype and shape (None when they need none)"""
+    dx = grads.get(XceptionEngine.INPUT)
+    return None if dx is None else dx.to(ctx.x_dtype).reshape(ctx.x_shape)

@@ -217,7 +217,7 @@ def dw_bwd(act, dY, X, Wt, scale, shift, dX, dW_out, N, H, W, C, dRes=None, dSki
            res_bn_input=None):
     """Returns (bnpart, P) -- the preceding BN's backward partial sums -- when bn_stats
     (that BN's Stats) is given, else (None, 0).  dW_out receives the weight gradient in the
-    nn.Conv2d [C][1][3][3] order (accumulate: added to it); Cw (default C): channels of the
+    nn.Conv2d [C][1][3][3] order (accumulate: added to it; None: not wanted); Cw (default C): channels of the
     weight when C is a padded channel pitch.  skip_pre: dSkip is a gradient of the same
     activation act(X) (it passes the activation mask and enters the BN partial sums).
     reduce_stream: run the weight-gradient slab reduction there (ordered after this launch);
@@ -244,7 +244,9 @@ def dw_bwd(act, dY, X, Wt, scale, shift, dX, dW_out, N, H, W, C, dRes=None, dSki
                   skip_geom[0], skip_geom[1], skip_geom[2], int(skip_pre), _p(dX), _p(part), _p(bnpart),
                   _p(bn_stats["mean"]) if bn_stats is not None else 0,
                   _p(bn_stats["invstd"]) if bn_stats is not None else 0, N, H, W, C, stream())
-    if batch is not None:
+    if dW_out is None:   # a frozen weight: the kernel's by-product partials are dropped
+        pass
+    elif batch is not None:
         batch.add(part, P, (Cw or C) * 9, dW_out, accumulate, ld=C * 9)
         if keep is not None:
             keep.append(part)
@@ -313,8 +315,9 @@ def row_stats(X, rows, C):
 
 
 def bn_backward_coef(dZ, Y, rows, C, bn, st, dgamma, dbeta, part=None, R=0, relu=False, accumulate=False, CP=None,
-                     narrow=False):
-    """BatchNorm2d backward (train-mode batch stats) up to the per-channel coefficients:
+                     narrow=False, frozen=False):
+    """BatchNorm2d backward (train-mode batch stats; frozen: running statistics, XCP_FIN_FROZEN -- st holds them,
+    bcoef = delta = 0) up to the per-channel coefficients:
     returns coef fp32 [3][C] (alpha, bcoef, delta: dY = alpha*dZ' + bcoef*Y + delta, dZ' the
     ReLU-masked dZ when relu) and writes (accumulate: adds to) dgamma/dbeta.
     ``part`` ([R][2][CP] partial (sum dz, sum dz*zhat)) may come fused from the
@@ -336,7 +339,7 @@ def bn_backward_coef(dZ, Y, rows, C, bn, st, dgamma, dbeta, part=None, R=0, relu
     part, R = _fold(part, R, CP)
     _lib.call("xcp_bn_bwd_finalize_part", _p(part), R, C, CP, float(rows), _p(bn["weight"]), _p(st["mean"]),
               _p(st["invstd"]), _p(coef), _p(coef[CP:]), _p(coef[2 * CP:]), _p(dgamma), _p(dbeta),
-              (1 if accumulate else 0) | (2 if narrow else 0), stream())
+              (1 if accumulate else 0) | (2 if narrow else 0) | (4 if frozen else 0), stream())
     return coef
 
 
@@ -371,7 +374,8 @@ def unit_bwd(G, Y, coef, Wt, X, dD, M, CO, CI, dW_out, accumulate=False):
     with _timed("unit_bwd", {"M": M, "CO": CO, "CI": CI}):
         _lib.call("xcp_unit_bwd", DT[G.dtype], _p(G), _p(Y), _p(coef), _p(coef[CO:]), _p(coef[2 * CO:]), _p(Wt),
                   _p(X), _p(dD), _p(P), M, CO, CI, S, rps, stream())
-    reduce_slabs(P, S, CO * CI, dW_out, accumulate)
+    if dW_out is not None:   # (None: a frozen weight, the kernel's by-product slabs are dropped)
+        reduce_slabs(P, S, CO * CI, dW_out, accumulate)
 
 
 def bn_act(X, Y, scale, shift, relu, rows, C):
@@ -450,6 +454,28 @@ def conv1_wgrad_bn(X, dZ, Y, coef, st, out, N, IH, IW, C, relu=True, accumulate=
         _lib.call("xcp_conv1_wgrad_bn", DT[dZ.dtype], _p(X), _p(dZ), _p(Y), _p(coef), _p(coef[C:]), _p(coef[2 * C:]),
                   ms, mt, _p(part), N, IH, IW, stream())
     reduce_slabs(part, R, 32 * 27, out, accumulate)
+
+
+def conv1_dgrad(dC1, W, dX, N, IH, IW):
+    """dX [N,3,IH,IW] fp32 = conv1's data gradient (the gradient w.r.t. the frames) of dC1 [N,OH,OW,32] (NHWC,
+    fp32 or bf16) with the fp32 [32,3,3,3] kernel W; every element of dX is written."""
+    check_gpu(dC1, W, dX)
+    if dX.dtype != torch.float32 or W.dtype != torch.float32 or dX.numel() != N * 3 * IH * IW or not dX.is_contiguous():
+        raise ValueError("conv1_dgrad: dX must be a contiguous fp32 [N,3,IH,IW] tensor and W fp32")
+    with _timed("conv1_dgrad", {"N": N, "IH": IH, "IW": IW}):
+        _lib.call("xcp_conv1_dgrad", DT[dC1.dtype], _p(dC1), _p(W), _p(dX), N, IH, IW, stream())
+
+
+def conv1_dgrad_bn(dZ, Y, W, coef, st, dX, N, IH, IW, C, relu=True):
+    """conv1's data gradient with BN1's backward apply fused: as bn_apply_coef(dZ, Y, dC1, coef, st, ..., relu)
+    followed by conv1_dgrad(dC1, W, dX, ...), bit for bit, without storing dC1 (C: the channel pitch of coef)."""
+    check_gpu(dZ, Y, W, dX)
+    if dX.dtype != torch.float32 or W.dtype != torch.float32 or dX.numel() != N * 3 * IH * IW or not dX.is_contiguous():
+        raise ValueError("conv1_dgrad_bn: dX must be a contiguous fp32 [N,3,IH,IW] tensor and W fp32")
+    ms, mt = (_p(st["scale"]), _p(st["shift"])) if relu else (0, 0)
+    with _timed("conv1_dgrad_bn", {"N": N, "IH": IH, "IW": IW}):
+        _lib.call("xcp_conv1_dgrad_bn", DT[dZ.dtype], _p(dZ), _p(Y), _p(W), _p(coef), _p(coef[C:]), _p(coef[2 * C:]),
+                  ms, mt, _p(dX), N, IH, IW, stream())
 
 
 def frames_u8_to_f32(frames, lengths, out):

@@ -351,17 +351,35 @@ def _(grad, x):
     return torch.empty((32, 3, 3, 3), device=x.device, dtype=torch.float32)
 
 
+@torch.library.custom_op("xcp::stem_conv1_dgrad", mutates_args=(), device_types="cuda")
+def stem_conv1_dgrad(grad: Tensor, weight: Tensor, IH: int, IW: int) -> Tensor:
+    """Gradient of Xception.conv1 w.r.t. its input frames: fp32 NCHW [N, 3, IH, IW] (contiguous, the
+    frames' layout) from the output gradient [N, 32, OH, OW] (fp32 or bf16)."""
+    with ops.device_guard(grad):
+        N, C, OH, OW = grad.shape
+        if C != 32 or IH < 3 or IW < 3 or (OH, OW) != ((IH - 3) // 2 + 1, (IW - 3) // 2 + 1):
+            raise ValueError(f"xcp::stem_conv1_dgrad: a {tuple(grad.shape)} gradient does not belong to {IH}x{IW} frames")
+        dx = torch.empty((N, 3, IH, IW), device=grad.device, dtype=torch.float32)
+        ops.conv1_dgrad(_cl(grad), weight.detach().float().contiguous(), dx, N, IH, IW)
+        return dx
+
+
+@stem_conv1_dgrad.register_fake
+def _(grad, weight, IH, IW):
+    return torch.empty((grad.shape[0], 3, IH, IW), device=grad.device, dtype=torch.float32)
+
+
 def _c1_setup(ctx, inputs, output):
     x, w, _ = inputs
-    ctx.save_for_backward(x)
+    ctx.save_for_backward(x, w)
 
 
 def _c1_bwd(ctx, grad):
-    (x,) = ctx.saved_tensors
-    if ctx.needs_input_grad[0]:
-        raise NotImplementedError("xcp::stem_conv1: no gradient w.r.t. the input frames (the reference never "
-                                  "differentiates w.r.t. its clips)")
-    return None, torch.ops.xcp.stem_conv1_wgrad(grad, x), None
+    x, w = ctx.saved_tensors
+    dx = None
+    if ctx.needs_input_grad[0]:   # saliency maps, adversarial inputs: the gradient w.r.t. the frames
+        dx = torch.ops.xcp.stem_conv1_dgrad(grad, w, x.shape[2], x.shape[3]).to(x.dtype)
+    return dx, torch.ops.xcp.stem_conv1_wgrad(grad, x), None
 
 
 stem_conv1.register_autograd(_c1_bwd, setup_context=_c1_setup)
@@ -573,4 +591,5 @@ lstm_varlen.register_autograd(_lstm_bwd, setup_context=_lstm_setup)
 
 OPS: List[str] = ["dwconv3x3", "dwconv3x3_backward", "pointwise", "pointwise_backward", "batch_norm",
                   "batch_norm_backward", "max_pool3x3s2", "max_pool3x3s2_backward", "stem_conv1", "stem_conv1_wgrad",
+                  "stem_conv1_dgrad",
                   "stem_conv2", "stem_conv2_backward", "lstm", "lstm_backward", "lstm_varlen", "lstm_varlen_backward"]
