@@ -354,6 +354,32 @@ int xcp_lstm_bwd_varlen(const float* dout, const float* dhn, const float* dcn, c
                         const float* gates, float* dgates, float* work, const int* lens, int B, int T, int H, int kernel,
                         xcp_stream_t stream);
 
+/* ---- LSTM recurrence from an initial state: nn.LSTM(...)(x, (h0, c0)) (lstm.hip, the same kernels) ----
+ * The reference op is nn.LSTM(I, H, 1, batch_first=True)(x, (h0, c0)), over packed input when lens is
+ * given.  h0 / c0 [B][H] fp32 (nn.LSTM's [1][B][H]) are h_{-1} / c_{-1} of every clip; lens is nullable
+ * (null: every clip has T steps; else as in xcp_lstm_fwd_varlen, clamped to [0, T]).
+ *   forward : the saved hprev[b][0] is h0[b] (the weight gradient dW_hh = dgates^T hprev must see it);
+ *             hn / cn are the state after step L - 1, and for L = 0 they are h0[b] / c0[b]: the state
+ *             passes through a clip that has no frame in this call (out / hprev rows of it are zero).
+ *   backward: step 0 takes c0 as c_{t-1} (null: zero); dh0[b] = sum_j dgates_0[b][j] W_hh[j][:] and
+ *             dc0[b] = dc_0 f_0; for L = 0, dh0 = dhn and dc0 = dcn (zero where those are null).  dh0 /
+ *             dc0 may each be null (not wanted).
+ * h0 and c0 are given together: one null and one not is XCP_EINVAL; both null is the call without a
+ * state.  They must not alias hn / cn.  Kernel by shape as for the varlen entries: register-resident
+ * (H = 64 / 128), per-step (H = 256 / 512 / 1024, B <= 32; the backward spends one more launch on dh0 /
+ * dc0) or generic; a call with a state never takes the persistent, gather or clip-grouped kernels.
+ * xcp_lstm_state_needs_whhT(B, H, kernel): 1 when the generic kernel runs (it reads whhT).
+ * xcp_lstm_bwd_state's work: as xcp_lstm_bwd_varlen's. */
+int xcp_lstm_state_needs_whhT(int B, int H, int kernel);
+/* nn.LSTM(...)(x, (h0, c0)) forward recurrence */
+int xcp_lstm_fwd_state(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh,
+                       const float* h0, const float* c0, float* out, float* hprev, float* cst, float* gates, float* hn,
+                       float* cn, const int* lens, int B, int T, int H, int kernel, xcp_stream_t stream);
+/* backward of nn.LSTM(...)(x, (h0, c0)), with d/dh0 and d/dc0 */
+int xcp_lstm_bwd_state(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* c0,
+                       const float* cst, const float* gates, float* dgates, float* dh0, float* dc0, float* work,
+                       const int* lens, int B, int T, int H, int kernel, xcp_stream_t stream);
+
 /* ---- diagnostic (bench.py only; no reference counterpart) ----
  * blocks workgroups (one per CU) each run `iters` x 4 back-to-back bf16 MFMAs; out: DEVICE int64
  * [2 * blocks + 256]: out[2b] = shader cycles of block b's loop, out[2b + 1] = 100 MHz real-time

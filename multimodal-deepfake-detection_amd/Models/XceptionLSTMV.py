@@ -58,3 +58,13 @@ class XceptionLSTMV(nn.Module):
             lstm_out = lstm_out[:, -1, :]
         dense_out = self.fc_layers(lstm_out)
         return self.sigmoid(self.fc_out(dense_out))
+
+    def forward_state(self, features, seq_lengths=None, state=None):
+        """``forward`` for a clip that arrives in chunks of frames: ``state`` is the ``(h, c)`` pair (each
+        [1,B,H]) the previous chunk returned, or None at the clip's start; returns ``(prob, (h_n, c_n))`` with
+        the probability of the clip so far.  A clip with no frame in this chunk (device ``seq_lengths`` entry
+        0) keeps its state, so its probability stays that of its last real frame.  ``forward`` keeps its
+        two-argument signature (tests pin it), so the state has a method of its own."""
+        _, (h_n, c_n) = self.lstm(features, state, lengths=seq_lengths)
+        dense_out = self.fc_layers(h_n[0])
+        return self.sigmoid(self.fc_out(dense_out)), (h_n, c_n)

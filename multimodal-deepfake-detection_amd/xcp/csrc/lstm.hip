@@ -33,6 +33,22 @@
 // runs over all B*T rows and 0 x (uninitialised) may be NaN; cst and gates are left unwritten there
 // and no kernel uses a value loaded from such a row (the per-step kernels load some as stand-in
 // addresses and select them away, as they do for absent operands).
+//
+// Initial state.  The same three families are templates on `bool ST` as well: ST = false is the kernel
+// above (h0 = c0 = 0; it never touches its state arguments, the last ones), ST = true starts clip b from
+// h0[b] / c0[b] (fp32 [B][H]) -- nn.LSTM(...)(x, (h0, c0)), with lengths the same over packed input:
+//   forward : h_{-1} = h0[b], c_{-1} = c0[b]; the saved hprev[b][0] is h0[b] (dW_hh = dgates^T hprev must
+//     see it); h_n / c_n are the state after step L - 1 and, for L = 0, h0[b] / c0[b] themselves, so the
+//     state passes through a clip that has no frame in this call (its out / hprev rows are zero as ever);
+//   backward: step 0 takes c0 as c_{t-1}; after it dh0[b] = sum_j dgates_0[b][j] W_hh[j][:] and
+//     dc0[b] = dc_0 f_0; for L = 0, dh0 = dh_n and dc0 = dc_n (zero where absent).  dh0 / dc0 may be null.
+//     The per-clip kernels hold exactly these values in their carries when the loop ends; the per-step
+//     backward forms dh_{t-1} in the next launch, so dh0 takes one more launch (t = -1) that runs the
+//     recurrent sum alone and copies the cell-gradient carry out of `work`.
+// One body again: hx = zeros is bit-identical to no state, and a sequence run in chunks with h_n / c_n
+// carried into h0 / c0 (and dh0 / dc0 back into dh_n / dc_n) is bit-identical to the whole run in out,
+// h_n, c_n, cst and dgates (tests/test_gpu_lstm_state.py).  A call with a state never takes the
+// persistent, gather or clip-grouped kernels: nothing new polls.  h0 / c0 must not alias h_n / c_n.
 #include "common.h"
 #include <stdlib.h>
 #include <mutex>
@@ -55,13 +71,14 @@ XCP_DEV int lstm_len(const int* __restrict__ lens, int b, int T) { return min(ma
 // xproj [B][T][4H] (already x W_ih^T); whhT [H][4H]; bias = b_ih + b_hh added here.
 // Outputs: out/h [B][T][H], hprev [B][T][H] (h_{t-1}), c [B][T][H],
 // gates [B][T][4H] post-activation (i, f, g, o), h_n / c_n [B][H].
-template <bool VL>
+template <bool VL, bool ST>
 __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__ xproj, const float* __restrict__ whhT,
                                                        const float* __restrict__ bih, const float* __restrict__ bhh,
                                                        float* __restrict__ out, float* __restrict__ hprev,
                                                        float* __restrict__ cst, float* __restrict__ gates,
                                                        float* __restrict__ hn, float* __restrict__ cn, int T, int H,
-                                                       const int* __restrict__ lens) {
+                                                       const int* __restrict__ lens, const float* __restrict__ h0,
+                                                       const float* __restrict__ c0) {
   extern __shared__ float sm[];   // h [H], c [H], gate pre-activations [4H]
   float* sh = sm;
   float* sc = sm + H;
@@ -69,7 +86,11 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
   const int b = blockIdx.x, tid = threadIdx.x;
   const int G4 = 4 * H;
   const int L = VL ? lstm_len(lens, b, T) : T;
-  for (int k = tid; k < H; k += blockDim.x) { sh[k] = 0.f; sc[k] = 0.f; }
+  if constexpr (ST) {   // h_{-1}, c_{-1}: step 0 saves h0 as its hprev, and L = 0 hands both on as h_n / c_n
+    for (int k = tid; k < H; k += blockDim.x) { sh[k] = h0[(long)b * H + k]; sc[k] = c0[(long)b * H + k]; }
+  } else {
+    for (int k = tid; k < H; k += blockDim.x) { sh[k] = 0.f; sc[k] = 0.f; }
+  }
   __syncthreads();
   for (int t = 0; t < L; ++t) {
     const float* xp = xproj + ((long)b * T + t) * G4;
@@ -113,12 +134,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
 // Backward through time.  dout [B][T][H] (may be null = zeros), dhn/dcn [B][H]
 // (may be null).  whh [4H][H] (row-major, as stored by nn.LSTM).
 // Writes dgates [B][T][4H] (pre-activation gradients).
-template <bool VL>
+template <bool VL, bool ST>
 __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ dhn,
                                                        const float* __restrict__ dcn, const float* __restrict__ whh,
                                                        const float* __restrict__ cst, const float* __restrict__ gates,
                                                        float* __restrict__ dgates, int T, int H,
-                                                       const int* __restrict__ lens) {
+                                                       const int* __restrict__ lens, const float* __restrict__ c0,
+                                                       float* __restrict__ dh0, float* __restrict__ dc0) {
   extern __shared__ float sm[];   // dh [H], dc [H], dgates_t [4H]
   float* sdh = sm;
   float* sdc = sm + H;
@@ -138,7 +160,9 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
     for (int k = tid; k < H; k += blockDim.x) {
       const float dh = sdh[k] + (dout ? dout[ob + k] : 0.f);
       const float c = cst[ob + k];
-      const float cp = t > 0 ? cst[ob - H + k] : 0.f;
+      float cp = 0.f;
+      if constexpr (ST) cp = t > 0 ? cst[ob - H + k] : (c0 ? c0[(long)b * H + k] : 0.f);
+      else cp = t > 0 ? cst[ob - H + k] : 0.f;
       const float ig = gt[k], fg = gt[H + k], gg = gt[2 * H + k], og = gt[3 * H + k];
       const float tc = tanhf(c);
       const float dO = dh * tc;
@@ -159,6 +183,12 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
     }
     __syncthreads();
   }
+  if constexpr (ST) {   // what is left after step 0 (for L = 0: dh_n / dc_n, or zero) is the state's gradient
+    for (int k = tid; k < H; k += blockDim.x) {
+      if (dh0) dh0[(long)b * H + k] = sdh[k];
+      if (dc0) dc0[(long)b * H + k] = sdc[k];
+    }
+  }
   if constexpr (VL) {   // tail rows t >= L: zero pre-activation gradients
     const long tb = ((long)b * T + L) * G4, tn = (long)(T - L) * G4;
     for (long e = tid; e < tn; e += blockDim.x) dgates[tb + e] = 0.f;
@@ -174,7 +204,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
 // except the per-step x-projection / state rows, which are prefetched one step ahead.
 //
 // forward: thread (gate j, part s), tid = j*S + s, holds W_hh[j][s*KPT .. +KPT).
-template <int H, bool VL>
+template <int H, bool VL, bool ST>
 __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restrict__ xproj,
                                                             const float* __restrict__ whh,
                                                             const float* __restrict__ bih,
@@ -182,7 +212,9 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
                                                             float* __restrict__ hprev, float* __restrict__ cst,
                                                             float* __restrict__ gates, float* __restrict__ hn,
                                                             float* __restrict__ cn, int T,
-                                                            const int* __restrict__ lens) {
+                                                            const int* __restrict__ lens,
+                                                            const float* __restrict__ h0,
+                                                            const float* __restrict__ c0) {
   constexpr int G4 = 4 * H, S = 1024 / G4, KPT = H / S, PADK = KPT + 4;
   static_assert(S >= 1 && KPT % 4 == 0, "unsupported H");
   __shared__ __attribute__((aligned(16))) float sh[S * PADK];   // h_{t-1}, part s at s*PADK (bank-spread)
@@ -200,8 +232,15 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
   const float bias = bih[j] + bhh[j];
   const bool gate_tanh = (j / H) == 2;
   auto hidx = [](int k) { return (k / KPT) * PADK + k % KPT; };
-  if (tid < H) sh[hidx(tid)] = 0.f;
   float c = 0.f;                                 // c_{t-1}[tid] for tid < H
+  if constexpr (ST) {   // h_{-1}, c_{-1} (for L = 0 they are handed on as h_n / c_n below)
+    if (tid < H) {
+      sh[hidx(tid)] = h0[(long)b * H + tid];
+      c = c0[(long)b * H + tid];
+    }
+  } else {
+    if (tid < H) sh[hidx(tid)] = 0.f;
+  }
   const float* xb = xproj + (long)b * T * G4;
   float xn = s == 0 ? xb[j] : 0.f;               // (row 0 exists for L = 0 too: T >= 1)
   __syncthreads();
@@ -261,7 +300,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
 // backward: thread (unit k, part p), tid = k*P + p, holds W_hh[p*JPT .. +JPT)[k]; the
 // step's pre-activation gradients are broadcast from LDS and dh_{t-1}[k] is reduced over
 // the P parts (adjacent lanes) by shuffles.
-template <int H, bool VL>
+template <int H, bool VL, bool ST>
 __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restrict__ dout,
                                                             const float* __restrict__ dhn,
                                                             const float* __restrict__ dcn,
@@ -269,7 +308,9 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
                                                             const float* __restrict__ cst,
                                                             const float* __restrict__ gates,
                                                             float* __restrict__ dgates, int T,
-                                                            const int* __restrict__ lens) {
+                                                            const int* __restrict__ lens,
+                                                            const float* __restrict__ c0,
+                                                            float* __restrict__ dh0, float* __restrict__ dc0) {
   constexpr int G4 = 4 * H, P = 1024 / H, JPT = G4 / P, PADJ = JPT + 4;
   static_assert(P >= 1 && JPT % 4 == 0, "unsupported H");
   __shared__ __attribute__((aligned(16))) float sdg[P * PADJ];
@@ -288,7 +329,8 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
     const long ob = ((long)b * T + t) * H + tid;
     const float* gt = gates + ((long)b * T + t) * G4;
     n_c = cst[ob];
-    n_cp = t > 0 ? cst[ob - H] : 0.f;
+    if constexpr (ST) n_cp = t > 0 ? cst[ob - H] : (c0 ? c0[(long)b * H + tid] : 0.f);
+    else n_cp = t > 0 ? cst[ob - H] : 0.f;
     n_i = gt[tid]; n_f = gt[H + tid]; n_g = gt[2 * H + tid]; n_o = gt[3 * H + tid];
     n_do = dout ? dout[ob] : 0.f;
   };
@@ -331,6 +373,12 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
     if (p == 0) sdh[k] = acc;
     __syncthreads();
   }
+  if constexpr (ST) {   // what is left after step 0 (for L = 0: dh_n / dc_n, or zero) is the state's gradient
+    if (tid < H) {
+      if (dh0) dh0[(long)b * H + tid] = sdh[tid];
+      if (dc0) dc0[(long)b * H + tid] = dc;
+    }
+  }
   if constexpr (VL) {   // tail rows t >= L (contiguous, 16-B aligned): zero pre-activation gradients
     const long n4 = (long)(T - L) * (G4 / 4);
     float4* pd = reinterpret_cast<float4*>(dgates + ((long)b * T + L) * G4);
@@ -359,13 +407,14 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
 constexpr int LS_UPW = 2;              // hidden units per workgroup
 constexpr int LS_MAXB = 32;            // clips (register partials per thread)
 
-template <int KS, bool VL>   // KS = H / 32 (k values per slice)
+template <int KS, bool VL, bool ST>   // KS = H / 32 (k values per slice)
 __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restrict__ xproj, const float* __restrict__ whh,
                                                             const float* __restrict__ bih, const float* __restrict__ bhh,
                                                             float* __restrict__ out, float* __restrict__ hprev,
                                                             float* __restrict__ cst, float* __restrict__ gates,
                                                             float* __restrict__ hn, float* __restrict__ cn, int B, int T,
-                                                            int t, const int* __restrict__ lens) {
+                                                            int t, const int* __restrict__ lens,
+                                                            const float* __restrict__ h0, const float* __restrict__ c0) {
   constexpr int H = KS * 32, G4 = 4 * H, PS = KS + 4;   // LDS slice pitch (floats)
   constexpr int RP = 33;                                // pitch of a (row, clip) partial row
   extern __shared__ float sm[];   // h_{t-1} [B][32][PS] (then the partials [8][B][RP]), then pre [8][B]
@@ -383,7 +432,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
   }
   // stage h_{t-1} (zero at t = 0): 8 loads in flight per thread -- unconditional (clamped index;
   // t = 0 reads step 0's slot as a stand-in and selects zero), since a load under a condition is
-  // issued and waited for on its own
+  // issued and waited for on its own.  With a state (ST) the t = 0 launch stages h0 [B][H] instead.
   const int n4 = B * H / 4;
   const int tp = t > 0 ? t - 1 : 0;
   for (int e0 = tid; e0 < n4; e0 += 8 * 256) {
@@ -392,7 +441,9 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
     for (int i = 0; i < 8; ++i) {
       const int e = min(e0 + i * 256, n4 - 1);
       const int b = e / (H / 4), k4 = (e - b * (H / 4)) * 4;
-      v[i] = *reinterpret_cast<const float4*>(out + ((long)b * T + tp) * H + k4);
+      const float* src = out + ((long)b * T + tp) * H + k4;
+      if constexpr (ST) src = t > 0 ? src : h0 + (long)b * H + k4;
+      v[i] = *reinterpret_cast<const float4*>(src);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -400,7 +451,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
       const int b = e / (H / 4), k4 = (e - b * (H / 4)) * 4;
       if (e < n4)
         *reinterpret_cast<float4*>(sh + (b * 32 + k4 / KS) * PS + (k4 % KS)) =
-            t > 0 ? v[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            ST || t > 0 ? v[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   __syncthreads();
@@ -461,22 +512,28 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
     const long ob = ((long)b * T + t) * H;
     const long op = t > 0 ? ob - H + k : ob + k;   // t = 0: a valid stand-in, selected away
     // (t > L: row t - 1 of cst was never written -- a valid address whose value is selected away)
-    const float vcp = cst[op], vhp = out[op];
-    const float cp = t > 0 ? vcp : 0.f;
+    const float* pcp = cst + op;
+    const float* php = out + op;
+    if constexpr (ST) {   // t = 0: the state itself
+      pcp = t > 0 ? pcp : c0 + (long)b * H + k;
+      php = t > 0 ? php : h0 + (long)b * H + k;
+    }
+    const float vcp = *pcp, vhp = *php;
+    const float cp = ST || t > 0 ? vcp : 0.f;
     const float c = fmaf(fg, cp, ig * gg);
     const float h = og * tanhf(c);
     float* gt = gates + ((long)b * T + t) * G4;
     if (live) { gt[k] = ig; gt[H + k] = fg; gt[2 * H + k] = gg; gt[3 * H + k] = og; }
-    hprev[ob + k] = live && t > 0 ? vhp : 0.f;
+    hprev[ob + k] = live && (ST || t > 0) ? vhp : 0.f;
     if (live) cst[ob + k] = c;
     out[ob + k] = live ? h : 0.f;
     if (t == L - 1) {
       hn[(long)b * H + k] = h;
       cn[(long)b * H + k] = c;
     }
-    if (VL && t == 0 && L == 0) {
-      hn[(long)b * H + k] = 0.f;
-      cn[(long)b * H + k] = 0.f;
+    if (VL && t == 0 && L == 0) {   // no frame: zero state, or the given one handed on
+      hn[(long)b * H + k] = ST ? vhp : 0.f;
+      cn[(long)b * H + k] = ST ? vcp : 0.f;
     }
   }
 }
@@ -500,12 +557,14 @@ __global__ __launch_bounds__(256) void lstm_transpose_kernel(const float* __rest
 // With lengths, clip b at t >= L writes zero dgates (so the recurrent sum into its step L - 1
 // vanishes on its own) and leaves its carry alone; at t = L - 1 it takes dhn / dcn as a full clip
 // does at T - 1.
-template <bool VL>
+template <bool VL, bool ST>
 __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restrict__ dout, const float* __restrict__ dhn,
                                                             const float* __restrict__ dcn, const float* __restrict__ whhT,
                                                             const float* __restrict__ cst, const float* __restrict__ gates,
                                                             float* __restrict__ dgates, float* __restrict__ dcw, int B,
-                                                            int T, int H, int t, const int* __restrict__ lens) {
+                                                            int T, int H, int t, const int* __restrict__ lens,
+                                                            const float* __restrict__ c0, float* __restrict__ dh0,
+                                                            float* __restrict__ dc0) {
   extern __shared__ float sm[];   // W columns [16 slices][SP] ([4H / 16][2] each), dh [B][2]
   const int G4 = 4 * H;
   const int per = G4 / 16, SP = 2 * per + 4;   // slice pitch: +4 floats, so the 16 slices of a
@@ -581,6 +640,15 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
   if (tid < B * LS_UPW) {
     const int b = tid / LS_UPW, v = tid - b * LS_UPW, k = u0 + v;
     const int L = VL ? lstm_len(lens, b, T) : T;
+    if constexpr (ST) {
+      if (t < 0) {   // the launch after step 0: only the recurrent sum above ran (over dgates_0)
+        const long bk = (long)b * H + k;
+        const bool none = VL && L == 0;   // no frame: dh_n / dc_n (or zero) pass through; the carry was never written
+        if (dh0) dh0[bk] = none ? (dhn ? dhn[bk] : 0.f) : sdh[b * 2 + v];
+        if (dc0) dc0[bk] = none ? (dcn ? dcn[bk] : 0.f) : dcw[bk];
+        return;
+      }
+    }
     const bool live = !VL || t < L;
     const long ob = ((long)b * T + t) * H, bk = (long)b * H + k;
     // every global load unconditional (absent operands, and every operand of a clip past its end,
@@ -591,7 +659,9 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
     const float vhn = *(last && dhn ? dhn + bk : pc);
     const float vcw = *(!last ? dcw + bk : (dcn ? dcn + bk : pc));
     const float vdo = *(dout ? dout + ob + k : pc);
-    const float vcp = *(t > 0 ? pc - H : pc);
+    const float* pcp = t > 0 ? pc - H : pc;
+    if constexpr (ST) pcp = t > 0 || !c0 ? pcp : c0 + bk;
+    const float vcp = *pcp;
     const float c = *pc;
     const float* gt = gates + ((long)b * T + t) * G4;
     const float ig = gt[k], fg = gt[H + k], gg = gt[2 * H + k], og = gt[3 * H + k];
@@ -599,7 +669,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
     const float dhr = !last ? sdh[b * 2 + v] : (dhn ? vhn : 0.f);
     const float dcr = !last || dcn ? vcw : 0.f;
     const float dh = dhr + (dout ? vdo : 0.f);
-    const float cp = t > 0 ? vcp : 0.f;
+    const float cp = t > 0 || (ST && c0) ? vcp : 0.f;
     const float tc = tanhf(c);
     const float dO = dh * tc;
     // dcr + dh * og * (1 - tc * tc) with its roundings spelled out: left to the compiler, one
@@ -1272,39 +1342,39 @@ int lp_sync(hipStream_t st, LstmSync& sy) {
 // the persistent, clip-grouped and gather kernels (those have no length-aware form).
 bool lstm_fwd_persist(int B, int H, int kernel, bool vl) { return !vl && lstm_persist(B, H, kernel, true); }
 
-// the register-resident, per-step or generic forward
-template <bool VL>
+// the register-resident, per-step or generic forward (ST: from the state h0 / c0 [B][H], both non-null)
+template <bool VL, bool ST = false>
 int lstm_fwd_launch(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh, float* out,
                     float* hprev, float* cst, float* gates, float* hn, float* cn, const int* lens, int B, int T, int H,
-                    int kernel, hipStream_t st) {
+                    int kernel, hipStream_t st, const float* h0 = nullptr, const float* c0 = nullptr) {
   if (lstm_reg(H, kernel)) {
     if (H == 128)
-      hipLaunchKernelGGL((lstm_fwd_reg_kernel<128, VL>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out, hprev,
-                         cst, gates, hn, cn, T, lens);
+      hipLaunchKernelGGL((lstm_fwd_reg_kernel<128, VL, ST>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out,
+                         hprev, cst, gates, hn, cn, T, lens, h0, c0);
     else
-      hipLaunchKernelGGL((lstm_fwd_reg_kernel<64, VL>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out, hprev,
-                         cst, gates, hn, cn, T, lens);
+      hipLaunchKernelGGL((lstm_fwd_reg_kernel<64, VL, ST>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out,
+                         hprev, cst, gates, hn, cn, T, lens, h0, c0);
     return (int)hipGetLastError();
   }
   if (lstm_step(B, H, kernel)) {
     const size_t smem = ((size_t)B * 32 * (H / 32 + 4) + 8 * B) * sizeof(float);
     for (int t = 0; t < T; ++t) {
       if (H == 256)
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<8, VL>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh,
-                           out, hprev, cst, gates, hn, cn, B, T, t, lens);
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<8, VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih,
+                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0);
       else if (H == 512)
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<16, VL>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh,
-                           out, hprev, cst, gates, hn, cn, B, T, t, lens);
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<16, VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih,
+                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0);
       else
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<32, VL>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih, bhh,
-                           out, hprev, cst, gates, hn, cn, B, T, t, lens);
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<32, VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih,
+                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0);
     }
     return (int)hipGetLastError();
   }
   if (!whhT) return XCP_EINVAL;
   const size_t smem = (size_t)6 * H * sizeof(float);
-  hipLaunchKernelGGL(lstm_fwd_kernel<VL>, dim3(B), dim3(256), smem, st, xproj, whhT, bih, bhh, out, hprev, cst, gates, hn,
-                     cn, T, H, lens);
+  hipLaunchKernelGGL((lstm_fwd_kernel<VL, ST>), dim3(B), dim3(256), smem, st, xproj, whhT, bih, bhh, out, hprev, cst,
+                     gates, hn, cn, T, H, lens, h0, c0);
   return (int)hipGetLastError();
 }
 
@@ -1335,33 +1405,35 @@ int lstm_needs_whhT(int B, int H, int kernel, bool vl) {
   return lstm_reg(H, kernel) || lstm_fwd_persist(B, H, kernel, vl) || lstm_step(B, H, kernel) ? 0 : 1;
 }
 
-// the per-step, register-resident or generic backward
-template <bool VL>
+// the per-step, register-resident or generic backward (ST: step 0 takes c0 [B][H] (null: zero) as c_{-1}, and
+// dh0 / dc0 [B][H], each nullable, receive the state's gradient; the per-step form spends one more launch
+// on them, which runs the recurrent sum over dgates_0 alone)
+template <bool VL, bool ST = false>
 int lstm_bwd_launch(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* cst,
                     const float* gates, float* dgates, float* work, const int* lens, int B, int T, int H, int kernel,
-                    hipStream_t st) {
+                    hipStream_t st, const float* c0 = nullptr, float* dh0 = nullptr, float* dc0 = nullptr) {
   if (lstm_step(B, H, kernel)) {
     if (!work) return XCP_EINVAL;
     float* whhT = work + (long)B * H;
     hipLaunchKernelGGL(lstm_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, st, whh, whhT, H);
     const size_t smem = ((size_t)8 * H + 64 + 2 * B) * sizeof(float);
-    for (int t = T - 1; t >= 0; --t)
-      hipLaunchKernelGGL(lstm_bwd_step_kernel<VL>, dim3(H / LS_UPW), dim3(256), smem, st, dout, dhn, dcn, whhT, cst, gates,
-                         dgates, work, B, T, H, t, lens);
+    for (int t = T - 1; t >= (ST && (dh0 || dc0) ? -1 : 0); --t)
+      hipLaunchKernelGGL((lstm_bwd_step_kernel<VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, dout, dhn, dcn, whhT, cst,
+                         gates, dgates, work, B, T, H, t, lens, c0, dh0, dc0);
     return (int)hipGetLastError();
   }
   if (lstm_reg(H, kernel)) {
     if (H == 128)
-      hipLaunchKernelGGL((lstm_bwd_reg_kernel<128, VL>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
-                         dgates, T, lens);
+      hipLaunchKernelGGL((lstm_bwd_reg_kernel<128, VL, ST>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
+                         dgates, T, lens, c0, dh0, dc0);
     else
-      hipLaunchKernelGGL((lstm_bwd_reg_kernel<64, VL>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
-                         dgates, T, lens);
+      hipLaunchKernelGGL((lstm_bwd_reg_kernel<64, VL, ST>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
+                         dgates, T, lens, c0, dh0, dc0);
     return (int)hipGetLastError();
   }
   const size_t smem = (size_t)6 * H * sizeof(float);
-  hipLaunchKernelGGL(lstm_bwd_kernel<VL>, dim3(B), dim3(256), smem, st, dout, dhn, dcn, whh, cst, gates, dgates, T, H,
-                     lens);
+  hipLaunchKernelGGL((lstm_bwd_kernel<VL, ST>), dim3(B), dim3(256), smem, st, dout, dhn, dcn, whh, cst, gates, dgates, T,
+                     H, lens, c0, dh0, dc0);
   return (int)hipGetLastError();
 }
 
@@ -1476,6 +1548,37 @@ int xcp_lstm_bwd_varlen(const float* dout, const float* dhn, const float* dcn, c
                         hipStream_t st) {
   if (B > 0 && T > 0 && (H <= 0 || !lens)) return XCP_EINVAL;
   return lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st);
+}
+
+// From an initial state: nn.LSTM(...)(x, (h0, c0)), with lengths (lens non-null) the same over packed input.
+// h0 / c0 [B][H] fp32, given together (both null: the plain call above); they must not alias hn / cn.  A call
+// with a state takes the register-resident, per-step or generic kernels only -- never one that polls.
+int xcp_lstm_state_needs_whhT(int B, int H, int kernel) { return lstm_reg(H, kernel) || lstm_step(B, H, kernel) ? 0 : 1; }
+
+int xcp_lstm_fwd_state(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh,
+                       const float* h0, const float* c0, float* out, float* hprev, float* cst, float* gates, float* hn,
+                       float* cn, const int* lens, int B, int T, int H, int kernel, hipStream_t st) {
+  if ((h0 == nullptr) != (c0 == nullptr)) return XCP_EINVAL;
+  if (B <= 0 || T <= 0) return XCP_OK;
+  if (H <= 0 || kernel < 0 || kernel > 1) return XCP_EINVAL;
+  if (!h0) return lstm_fwd(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H, kernel, st);
+  return lens ? lstm_fwd_launch<true, true>(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H,
+                                            kernel, st, h0, c0)
+              : lstm_fwd_launch<false, true>(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, lens, B, T, H,
+                                             kernel, st, h0, c0);
+}
+
+// Backward of the above: c0 [B][H] is step 0's c_{t-1} (null: zero); dh0 / dc0 [B][H] receive d/dh0 and d/dc0
+// (each nullable: not wanted).  work as for xcp_lstm_bwd_varlen.
+int xcp_lstm_bwd_state(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* c0,
+                       const float* cst, const float* gates, float* dgates, float* dh0, float* dc0, float* work,
+                       const int* lens, int B, int T, int H, int kernel, hipStream_t st) {
+  if (B <= 0 || T <= 0) return XCP_OK;
+  if (H <= 0 || kernel < 0 || kernel > 1) return XCP_EINVAL;
+  return lens ? lstm_bwd_launch<true, true>(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st, c0,
+                                            dh0, dc0)
+              : lstm_bwd_launch<false, true>(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st, c0,
+                                             dh0, dc0);
 }
 
 }  // extern "C"

@@ -16,19 +16,22 @@ Zero-padded clips of unequal length (the loaders' ``seq_lengths``) go through
 ``torch.ops.xcp.lstm_varlen`` (the same kernels in lstm.hip), either as ``lstm(x, lengths=...)`` or as a
 ``PackedSequence`` input, with the semantics of ``pack_padded_sequence`` -> ``nn.LSTM`` ->
 ``pad_packed_sequence``.
+
+An initial state ``hx = (h0, c0)`` goes through ``torch.ops.xcp.lstm_state`` (state-aware instantiations of
+the same kernels), with or without lengths: a long clip can be fed in chunks of frames with the state
+carried from one chunk to the next (xcp/streaming.py), and ``h0`` / ``c0`` are differentiable.
 """
 import torch
 import torch.nn as nn
 from torch.nn.utils.rnn import PackedSequence, pack_padded_sequence, pad_packed_sequence
 
-from . import torch_ops  # noqa: F401  (registers torch.ops.xcp.lstm, torch.ops.xcp.lstm_varlen)
+from . import torch_ops  # noqa: F401  (registers torch.ops.xcp.lstm, .lstm_varlen, .lstm_state)
 
 
 class LSTM(nn.LSTM):
     """nn.LSTM with the xcp forward.  Supported configuration (the reference's):
-    num_layers=1, batch_first=True, unidirectional, bias=True, proj_size=0, no
-    initial state.  ``xcp_kernel`` (attribute): 0 = automatic recurrence kernel choice,
-    1 = the generic kernels.
+    num_layers=1, batch_first=True, unidirectional, bias=True, proj_size=0.
+    ``xcp_kernel`` (attribute): 0 = automatic recurrence kernel choice, 1 = the generic kernels.
 
     ``forward(input, hx=None, lengths=None)``: with ``lengths`` (int32 / int64 ``[B]``) clip ``b`` is
     ``input[b, :lengths[b]]`` and the rest of its rows is padding: ``out[b, t >= L]`` is zero, ``h_n`` /
@@ -37,25 +40,41 @@ class LSTM(nn.LSTM):
     validated (``1 <= L <= T``, as ``pack_padded_sequence`` demands); a device tensor is passed to the
     kernels unread -- they clamp it to ``[0, T]``, and a clip of length 0 gives zero outputs, states and
     gradients -- so the call stays capturable in a HIP graph.  A ``PackedSequence`` input is unpacked,
-    run the same way and returned packed, with ``h_n`` / ``c_n`` in the caller's batch order."""
+    run the same way and returned packed, with ``h_n`` / ``c_n`` in the caller's batch order.
+
+    ``hx = (h0, c0)``, each floating ``[1, B, H]`` on the input's device as ``nn.LSTM`` takes them (for a
+    ``PackedSequence`` in the caller's batch order), starts every clip from that state; both receive
+    gradients.  The state is kept in fp32 whatever dtype it comes in.  With device lengths a clip of length
+    0 hands its state on unchanged (``h_n = h0``, ``c_n = c0``, ``d/dh0 = d/dh_n``, ``d/dc0 = d/dc_n``), which
+    is what carries a short clip's state through the later chunks of a batch.  A call with ``hx`` runs the
+    register-resident, per-step or generic kernels, never the persistent ones; ``hx=None`` calls exactly the
+    ops it always did."""
 
     xcp_kernel = 0
 
     def forward(self, input, hx=None, lengths=None):  # noqa: A002  (nn.LSTM signature)
-        if (self.num_layers != 1 or not self.batch_first or self.bidirectional or not self.bias or self.proj_size
-                or hx is not None):
+        if self.num_layers != 1 or not self.batch_first or self.bidirectional or not self.bias or self.proj_size:
             raise NotImplementedError("xcp LSTM supports the reference configuration only "
-                                      "(1 layer, batch_first, unidirectional, bias, zero initial state)")
+                                      "(1 layer, batch_first, unidirectional, bias, no projection)")
         if isinstance(input, PackedSequence):
             if lengths is not None:
                 raise ValueError("a PackedSequence carries its own lengths; do not pass lengths= with it")
-            return self._forward_packed(input)
+            return self._forward_packed(input, hx)
         if input.dim() != 3:
             raise NotImplementedError("xcp LSTM expects batched [B, T, F] input")
         if lengths is not None:
             lengths = self._check_lengths(lengths, input.shape[0], input.shape[1])
+        if hx is not None:
+            h0, c0 = self._check_hx(hx, input)
         if not input.is_cuda:
             raise RuntimeError("xcp LSTM runs on the MI355X only (got a non-GPU tensor); there is no CPU fallback")
+        if hx is not None:
+            if lengths is not None:
+                lengths = lengths.to(device=input.device, dtype=torch.int32).contiguous()
+            out, hn, cn, _, _, _ = torch.ops.xcp.lstm_state(
+                input, self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0, h0, c0, lengths,
+                int(self.xcp_kernel))
+            return out.to(input.dtype), (hn, cn)
         if lengths is not None:
             out, hn, cn, _, _, _ = torch.ops.xcp.lstm_varlen(
                 input, self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0,
@@ -77,10 +96,29 @@ class LSTM(nn.LSTM):
                 raise ValueError(f"lengths must lie in [1, {T}] (the padded length), got [{lo}, {hi}]")
         return lengths
 
-    def _forward_packed(self, packed):
-        """Compatibility path: plain torch gathers around the length-aware op."""
+    def _check_hx(self, hx, input):  # noqa: A002
+        """(h0, c0), each floating [1, B, H] on the input's device; refused in nn.LSTM's words where it has any"""
+        if not isinstance(hx, (tuple, list)) or len(hx) != 2 or not all(torch.is_tensor(t) for t in hx):
+            raise ValueError("hx must be a tuple of two tensors (h_0, c_0)")
+        B, H = input.shape[0], self.hidden_size
+        for i, t in enumerate(hx):
+            if t.dim() != 3:
+                raise RuntimeError("For batched 3-D input, hx and cx should also be 3-D but got "
+                                   f"({hx[0].dim()}-D, {hx[1].dim()}-D) tensors")
+            if tuple(t.shape) != (1, B, H):
+                raise RuntimeError(f"Expected hidden[{i}] size {(1, B, H)}, got {list(t.shape)}")
+            if not t.is_floating_point():
+                raise ValueError(f"hx[{i}] must be a floating-point tensor, got {t.dtype}")
+            if t.device != input.device:
+                raise RuntimeError("Input and hidden tensors are not at the same device, found input tensor at "
+                                   f"{input.device} and hidden tensor at {t.device}")
+        return hx[0], hx[1]
+
+    def _forward_packed(self, packed, hx=None):
+        """Compatibility path: plain torch gathers around the length-aware op (hx, like h_n / c_n, is in the
+        caller's batch order, which is the order the padded batch is run in)."""
         x, lens = pad_packed_sequence(packed, batch_first=True)   # caller's batch order, lens on the CPU
-        out, (hn, cn) = self.forward(x, lengths=lens)
+        out, (hn, cn) = self.forward(x, hx, lengths=lens)
         si = packed.sorted_indices
         if si is not None:
             out, lens = out.index_select(0, si), lens.index_select(0, si.to(lens.device))

@@ -613,8 +613,20 @@ def clock_probe(device, launches=8, iters=40000):
 # 1 = the generic kernels (tests pin them at shapes the specialised kernels also cover).
 # lens: None, or the per-clip lengths as an int32 [B] device tensor, clamped to [0, T] by the kernels
 # and never read on the host; a call with lengths never takes the persistent kernels (lstm.hip).
-def lstm_needs_whhT(B, H, kernel=0, lens=None):
+# h0 / c0: None, or the initial state as fp32 [B, H] (or [1, B, H]) device tensors, given together
+# (nn.LSTM(...)(x, (h0, c0))); dh0 / dc0: fp32 outputs of the same shape for the state's gradient, each
+# optional.  A call with any of them goes to the state entry points, which never take the persistent kernels.
+def lstm_needs_whhT(B, H, kernel=0, lens=None, state=False):
+    if state:
+        return _lib.call("xcp_lstm_state_needs_whhT", B, H, kernel) != 0
     return _lib.call("xcp_lstm_needs_whhT" if lens is None else "xcp_lstm_varlen_needs_whhT", B, H, kernel) != 0
+
+
+def _check_state(t, name, ref, B, H):
+    if (t.dtype != torch.float32 or t.device != ref.device or t.numel() != B * H or t.shape[-2:] != (B, H)
+            or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous fp32 [{B}, {H}] tensor on {ref.device}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
 
 
 def _check_lens(lens, ref, B):
@@ -623,7 +635,18 @@ def _check_lens(lens, ref, B):
                          f"{tuple(lens.shape)} on {lens.device}")
 
 
-def lstm_fwd(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, B, T, H, kernel=0, lens=None):
+def lstm_fwd(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, B, T, H, kernel=0, lens=None, h0=None,
+             c0=None):
+    if (h0 is None) != (c0 is None):
+        raise ValueError("h0 and c0 are given together")
+    if h0 is not None:
+        _check_state(h0, "h0", out, B, H)
+        _check_state(c0, "c0", out, B, H)
+        if lens is not None:
+            _check_lens(lens, out, B)
+        _lib.call("xcp_lstm_fwd_state", *(_p(t) for t in (xproj, whh, whhT, bih, bhh, h0, c0, out, hprev, cst, gates,
+                                                          hn, cn, lens)), B, T, H, kernel, stream())
+        return
     ptrs = [_p(t) for t in (xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn)]
     if lens is None:
         _lib.call("xcp_lstm_fwd", *ptrs, B, T, H, kernel, stream())
@@ -638,10 +661,20 @@ def lstm_sync_error():
     return _lib.call("xcp_lstm_sync_error")
 
 
-def lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, B, T, H, kernel=0, lens=None):
+def lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, B, T, H, kernel=0, lens=None, c0=None, dh0=None, dc0=None):
     # per-step kernels: cell-gradient carry [B][H] + W_hh^T [H][4H]; persistent kernels (never with lengths):
     # the dh partials [2][B][H / 4][H / 4][4] (include/xcp.h)
     n = B * H + 4 * H * H
+    if c0 is not None or dh0 is not None or dc0 is not None:
+        for t, name in ((c0, "c0"), (dh0, "dh0"), (dc0, "dc0")):
+            if t is not None:
+                _check_state(t, name, dgates, B, H)
+        if lens is not None:
+            _check_lens(lens, dgates, B)
+        work = torch.empty(n, device=whh.device, dtype=torch.float32)
+        _lib.call("xcp_lstm_bwd_state", *(_p(t) for t in (dout, dhn, dcn, whh, c0, cst, gates, dgates, dh0, dc0, work,
+                                                          lens)), B, T, H, kernel, stream())
+        return
     work = torch.empty(n if lens is not None else max(n, B * H * H // 2), device=whh.device, dtype=torch.float32)
     ptrs = [_p(t) for t in (dout, dhn, dcn, whh, cst, gates, dgates, work)]
     if lens is None:

@@ -439,11 +439,13 @@ stem_conv2.register_autograd(_c2_bwd, setup_context=_c2_setup)
 # ------------------------------------------------------------------ LSTM (nn.LSTM, 1 layer, batch_first)
 # xcp::lstm / xcp::lstm_backward and their forms with per-clip lengths, xcp::lstm_varlen /
 # xcp::lstm_varlen_backward, are the same code: the helpers below take lengths=None for the former.
+# xcp::lstm_state / xcp::lstm_state_backward (an initial state, with or without lengths) pass h0 / c0 as well.
 _LstmOut = Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]
 _LstmGrads = Tuple[Tensor, Tensor, Tensor, Tensor]
+_LstmStateGrads = Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]
 
 
-def _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel, lengths=None):
+def _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel, lengths=None, h0=None, c0=None):
     with ops.device_guard(x):
         ops.check_gpu(x, w_ih)
         B, T, I = x.shape
@@ -454,7 +456,9 @@ def _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel, lengths=None):
         ops.gemm_nt(xf, w_ih.detach().float().contiguous(), xproj, B * T, 4 * H, I)
         whh = w_hh.detach().float().contiguous()
         whhT = None
-        if ops.lstm_needs_whhT(B, H, kernel, lengths):
+        if h0 is not None:
+            h0, c0 = h0.detach().float().contiguous(), c0.detach().float().contiguous()
+        if ops.lstm_needs_whhT(B, H, kernel, lengths, state=h0 is not None):
             whhT = torch.empty(H * 4 * H, device=dev, dtype=torch.float32)
             ops.permute3(whh, whhT, 4 * H, H, 1, (1, 0, 2))
         out = torch.empty(B, T, H, device=dev, dtype=torch.float32)
@@ -464,7 +468,7 @@ def _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel, lengths=None):
         hn = torch.empty(1, B, H, device=dev, dtype=torch.float32)
         cn = torch.empty(1, B, H, device=dev, dtype=torch.float32)
         ops.lstm_fwd(xproj, whh, whhT, b_ih.detach().float().contiguous(), b_hh.detach().float().contiguous(), out,
-                     hprev, cst, gates, hn, cn, B, T, H, kernel, lengths)
+                     hprev, cst, gates, hn, cn, B, T, H, kernel, lengths, h0, c0)
         return out, hn, cn, hprev, cst, gates
 
 
@@ -476,7 +480,10 @@ def _lstm_forward_fake(x, w_hh):
             torch.empty(B, T, H, **f), torch.empty(B, T, 4 * H, **f))
 
 
-def _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx, lengths=None):
+def _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx, lengths=None, c0=None,
+                   need_dh0=False, need_dc0=False):
+    """With c0 (a call from an initial state) the result grows by (dh0, dc0), each [1, B, H], or empty where
+    not wanted: then the kernels do no work for it."""
     with ops.device_guard(x):
         B, T, I = x.shape
         H = w_hh.shape[1]
@@ -485,8 +492,15 @@ def _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, nee
         xf = x.detach().float().contiguous()
         dgates = torch.empty(M, 4 * H, device=dev, dtype=torch.float32)
         f32 = lambda t: None if t is None else t.float().contiguous()   # noqa: E731
-        ops.lstm_bwd(f32(dout), f32(dhn), f32(dcn), w_hh.detach().float().contiguous(), cst, gates, dgates, B, T, H,
-                     kernel, lengths)
+        if c0 is None:
+            ops.lstm_bwd(f32(dout), f32(dhn), f32(dcn), w_hh.detach().float().contiguous(), cst, gates, dgates, B, T, H,
+                         kernel, lengths)
+        else:
+            state = lambda want: torch.empty((1, B, H) if want else 0, device=dev, dtype=torch.float32)   # noqa: E731
+            dh0, dc0 = state(need_dh0), state(need_dc0)
+            ops.lstm_bwd(f32(dout), f32(dhn), f32(dcn), w_hh.detach().float().contiguous(), cst, gates, dgates, B, T, H,
+                         kernel, lengths, c0=f32(c0.detach()), dh0=dh0 if need_dh0 else None,
+                         dc0=dc0 if need_dc0 else None)
         dw_ih = torch.empty(4 * H, I, device=dev, dtype=torch.float32)
         ops.weight_grad(dgates, xf, M, 4 * H, I, dw_ih)
         dw_hh = torch.empty(4 * H, H, device=dev, dtype=torch.float32)
@@ -500,6 +514,8 @@ def _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, nee
             ops.gemm_nt(dgates, wT, dx, M, I, 4 * H)
         else:
             dx = torch.empty(0, device=dev, dtype=torch.float32)
+        if c0 is not None:
+            return dx, dw_ih, dw_hh, db, dh0, dc0
         return dx, dw_ih, dw_hh, db
 
 
@@ -589,7 +605,63 @@ def _(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, lengths, kernel, need_dx
 lstm_varlen.register_autograd(_lstm_bwd, setup_context=_lstm_setup)
 
 
+@torch.library.custom_op("xcp::lstm_state", mutates_args=(), device_types="cuda")
+def lstm_state(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, h0: Tensor, c0: Tensor,
+               lengths: Optional[Tensor], kernel: int) -> _LstmOut:
+    """``nn.LSTM(I, H, 1, batch_first=True)(x, (h0, c0))``: ``xcp::lstm`` (lengths None) or ``xcp::lstm_varlen``
+    started from the state h0 / c0 [1, B, H].  The saved hprev[:, 0] is h0; h_n / c_n of a clip of length 0 are
+    h0 / c0 themselves, so a state passes through a chunk in which its clip has no frame (lstm.hip).  Runs the
+    register-resident, per-step or generic kernels, never the persistent ones."""
+    return _lstm_forward(x, w_ih, w_hh, b_ih, b_hh, kernel, lengths, h0, c0)
+
+
+@lstm_state.register_fake
+def _(x, w_ih, w_hh, b_ih, b_hh, h0, c0, lengths, kernel):
+    return _lstm_forward_fake(x, w_hh)
+
+
+@torch.library.custom_op("xcp::lstm_state_backward", mutates_args=(), device_types="cuda")
+def lstm_state_backward(dout: Optional[Tensor], dhn: Optional[Tensor], dcn: Optional[Tensor], x: Tensor, w_ih: Tensor,
+                        w_hh: Tensor, c0: Tensor, hprev: Tensor, cst: Tensor, gates: Tensor,
+                        lengths: Optional[Tensor], kernel: int, need_dx: bool, need_dh0: bool,
+                        need_dc0: bool) -> _LstmStateGrads:
+    """(dx, dw_ih, dw_hh, db, dh0, dc0); dh0 / dc0 are [1, B, H], or empty when not wanted."""
+    return _lstm_backward(dout, dhn, dcn, x, w_ih, w_hh, hprev, cst, gates, kernel, need_dx, lengths, c0, need_dh0,
+                          need_dc0)
+
+
+@lstm_state_backward.register_fake
+def _(dout, dhn, dcn, x, w_ih, w_hh, c0, hprev, cst, gates, lengths, kernel, need_dx, need_dh0, need_dc0):
+    H = w_hh.shape[1]
+    f = dict(device=x.device, dtype=torch.float32)
+    state = lambda want: torch.empty((1, x.shape[0], H) if want else 0, **f)   # noqa: E731
+    return (*_lstm_backward_fake(x, w_ih, w_hh, need_dx), state(need_dh0), state(need_dc0))
+
+
+def _lstm_state_setup(ctx, inputs, output):
+    x, w_ih, w_hh, b_ih, b_hh, h0, c0, lengths, kernel = inputs
+    out, hn, cn, hprev, cst, gates = output
+    ctx.save_for_backward(x, w_ih, w_hh, c0, hprev, cst, gates, *(() if lengths is None else (lengths,)))
+    ctx.kernel = kernel
+    ctx.x_dtype, ctx.h_dtype, ctx.c_dtype = x.dtype, h0.dtype, c0.dtype
+    ctx.mark_non_differentiable(hprev, cst, gates)
+
+
+def _lstm_state_bwd(ctx, dout, dhn, dcn, *_):
+    x, w_ih, w_hh, c0, hprev, cst, gates, *lengths = ctx.saved_tensors
+    need_dx, need_dh0, need_dc0 = ctx.needs_input_grad[0], ctx.needs_input_grad[5], ctx.needs_input_grad[6]
+    dx, dw_ih, dw_hh, db, dh0, dc0 = torch.ops.xcp.lstm_state_backward(
+        dout, dhn, dcn, x, w_ih, w_hh, c0, hprev, cst, gates, lengths[0] if lengths else None, ctx.kernel, need_dx,
+        need_dh0, need_dc0)
+    return (dx.to(ctx.x_dtype) if need_dx else None, dw_ih, dw_hh, db, db.clone(),
+            dh0.to(ctx.h_dtype) if need_dh0 else None, dc0.to(ctx.c_dtype) if need_dc0 else None, None, None)
+
+
+lstm_state.register_autograd(_lstm_state_bwd, setup_context=_lstm_state_setup)
+
+
 OPS: List[str] = ["dwconv3x3", "dwconv3x3_backward", "pointwise", "pointwise_backward", "batch_norm",
                   "batch_norm_backward", "max_pool3x3s2", "max_pool3x3s2_backward", "stem_conv1", "stem_conv1_wgrad",
                   "stem_conv1_dgrad",
-                  "stem_conv2", "stem_conv2_backward", "lstm", "lstm_backward", "lstm_varlen", "lstm_varlen_backward"]
+                  "stem_conv2", "stem_conv2_backward", "lstm", "lstm_backward", "lstm_varlen", "lstm_varlen_backward",
+                  "lstm_state", "lstm_state_backward"]
