@@ -1051,9 +1051,11 @@ int xcp_conv1_wgrad_parts(int N, int IH, int IW) {
   return (int)blocks;
 }
 
-// 1 when the row kernel (and so xcp_conv1_wgrad_bn) takes this shape: bf16, frames <= 320 wide
+// 1 when the row kernel (and so xcp_conv1_wgrad_bn) takes this shape: bf16, frames 4 .. 320 wide (xrow_chunks
+// ends a row's last 16-B chunk at column IW - 1: a 3-wide frame's would start one float before the row;
+// the tile kernels' stage_rows zero-fills any IW >= 3)
 int xcp_conv1_wgrad_fused(int dtype, int IH, int IW) {
-  return dtype == XCP_BF16 && IW >= 3 && IH >= 3 && IW <= W1R_IW && 3L * IH * IW < (1L << 30);
+  return dtype == XCP_BF16 && IW >= 4 && IH >= 3 && IW <= W1R_IW && 3L * IH * IW < (1L << 30);
 }
 
 int xcp_conv1_wgrad(int dtype, const float* X, const void* dY, float* part, int N, int IH, int IW, hipStream_t st) {

@@ -40,6 +40,12 @@ The references are plain tensor ops in fp64 (the depthwise one nine shifted slic
 tensor); they run on whatever device their inputs are on, so the CPU emulations of
 test_elementwise_cpu.py and the kernels of test_gpu_elementwise.py are judged by the same code.
 All image tensors are NHWC.
+
+The second half (stem conv1 / conv2 gradients, channel reductions, BN finalize kernels) serves
+test_gpu_elementwise_stem_bn.py, which judges the kernels' outputs on the CPU: the conv references are fp64
+F.conv2d / conv2d_weight there.  Two more allowances are derived next to their references: the split-bf16
+products of the conv1 row kernels (conv1_ref) and the per-output rounding counts of the finalize kernels
+(bn_finalize_ref, bn_bwd_finalize_ref; judged by assert_within, since their bounds are not sums of n terms).
 """
 import torch
 import torch.nn.functional as F
@@ -341,3 +347,357 @@ def conv3x3_valid_ref(a, w, flip=None):
             if flip is not None:
                 extra += flip[:, ky:ky + OH, kx:kx + OW] @ wt.abs()
     return ref, ab, extra
+
+
+# ------------------------------------------------------------------ stem conv1 (csrc/stem.hip): 3 -> 32, 3x3, stride 2, valid
+U_SPLIT = 2.0 ** -18      # what x - hi - lo leaves of x after the bf16 head / tail split (see conv1_ref)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2).contiguous()
+
+
+def conv1_out(IH, IW):
+    return (IH - 3) // 2 + 1, (IW - 3) // 2 + 1
+
+
+def conv1_path(bf16_out, IW, wgrad=False):
+    """Which kernel xcp_conv1_fwd / xcp_conv1_wgrad launches, restated from the launchers:
+    "row"   bf16 and 4 <= IW <= 320 (xcp_conv1_wgrad_fused): split-bf16 MFMA products
+    "tile"  the LDS budget holds: forward (27 pitch + 864) floats, weight gradient 15 pitch floats + two rows of fp32 dY
+    "pixel" wider frames.   pitch = IW rounded up to 64."""
+    if bf16_out and 4 <= IW <= 320:
+        return "row"
+    pitch = (IW + 63) // 64 * 64
+    if wgrad:
+        return "tile" if 15 * pitch * 4 + 2 * conv1_out(3, IW)[1] * 32 * 4 <= 65536 else "pixel"
+    return "tile" if (27 * pitch + 864) * 4 <= 65536 else "pixel"
+
+
+CONV1_TILE_WIDEST = 512   # (27 * 512 + 864) * 4 = 58752 <= 65536; pitch 576 gives 65664
+
+
+def conv1_ref(x, w, split=False):
+    """x fp32 [N,3,IH,IW], w fp32 [32,3,3,3] -> (ref64, abs_terms, extra) [N,OH,OW,32], n = 27: fp64 F.conv2d of
+    the values and of their magnitudes (an fp32 x fp32 product is exact in fp64).
+
+    split: the forward row kernel's allowance.  It multiplies on the matrix cores with both operands split into
+    a bf16 head and tail, hi = bf16(x), lo = bf16(x - hi).  Counting bf16's 8 significant bits as
+    |x - hi| <= 2^-9 |x| and |x - hi - lo| <= 2^-18 |x| = r_x, the three products hi.hi + lo.hi + hi.lo miss
+    r_x w + x r_w + lo_x lo_w, so extra = 3 * 2^-18 (1 + 2^-8) abs_terms (test_gpu_conv1_dgrad.py quotes 2^-17
+    for the same products).  Round-to-nearest's strict worst case is half an ulp of 2^-7, i.e. 2^-8 and 2^-16:
+    the allowance is a quarter of the worst case of one term, and it is what 27 terms of either sign are held
+    to.  The weight-gradient row kernel splits X only (dC1 is bf16 already): 2^-18 abs_terms
+    (conv1_wgrad_ref).  The tile and per-pixel kernels are plain fp32 FMAs: no extra."""
+    xd, wd = x.double(), w.double()
+    ref = _nhwc(F.conv2d(xd, wd, None, 2))
+    ab = _nhwc(F.conv2d(xd.abs(), wd.abs(), None, 2))
+    extra = ab * (3 * U_SPLIT * (1 + 2.0 ** -8)) if split else torch.zeros_like(ab)
+    return ref, ab, extra
+
+
+def conv1_wgrad_ref(x, dy, split=False, flip=None):
+    """x fp32 [N,3,IH,IW], dy [N,OH,OW,32] (NHWC, any dtype) -> (ref64 [32,3,3,3], abs_terms, extra, n): fp64
+    conv2d_weight of the values and of the magnitudes; n = the number of output pixels at which dy is nonzero
+    (an exactly-zero term adds no rounding, wherever it falls in the summation tree).  split: the row kernel's
+    2^-18 abs_terms (conv1_ref); flip: a per-element allowance of dy (tie_flip of a restated dC1), carried
+    through |x|."""
+    xd, g = x.double(), _nchw(dy.double())
+    wg = lambda a, b: torch.nn.grad.conv2d_weight(a, (32, 3, 3, 3), b, stride=2)
+    ref, ab = wg(xd, g), wg(xd.abs(), g.abs())
+    extra = ab * U_SPLIT if split else torch.zeros_like(ab)
+    if flip is not None:
+        extra = extra + wg(xd.abs(), _nchw(flip.double()))
+    n = int((dy != 0).any(-1).sum())
+    return ref, ab, extra, n
+
+
+def conv1_stats_ref(Y, N, OH, OW, R):
+    """conv1_fwd_stats: partial row r = (sum y, sum y^2) over the STORED bf16 outputs of the output rows (tiles)
+    r, r + R, ... (a bf16 square is exact in fp32) -> (ref64 [R,2,32], abs_terms, n [R,1,1] = OW * tiles of r)"""
+    T = N * OH
+    y = Y.double().view(T, OW, 32)
+    ref = torch.zeros(R, 2, 32, dtype=torch.float64, device=Y.device)
+    ab = torch.zeros_like(ref)
+    for r in range(R):
+        t = y[r::R]
+        ref[r, 0], ref[r, 1] = t.sum((0, 1)), (t * t).sum((0, 1))
+        ab[r, 0], ab[r, 1] = t.abs().sum((0, 1)), ref[r, 1]
+    tiles = torch.tensor([len(range(r, T, R)) for r in range(R)], dtype=torch.float64, device=Y.device)
+    return ref, ab, (tiles * OW).view(R, 1, 1)
+
+
+def conv1_inputs(N, IH, IW, seed=1):
+    """signed frames (rand - 0.3: the sums cancel, abs_terms is not the result itself), kernel, dense gradient.
+    (The split products leave about 0.5 % of the row kernel's outputs not rounded to nearest; of the 256 outputs
+    of (2, 9, 4) that is one or two, and under seeds 0 and 2 three; and the weight gradient of that shape sums
+    8 pixels only, so its split residuals hardly average: seeds 3 and 4 reach 1.09 and 1.03 of the 2^-18 allowance
+    (see conv1_ref on its worst case).  Both are conditions on the data, as for `exclude`: seed 1.)"""
+    g = torch.Generator().manual_seed(100003 * seed + 977 * N + 31 * IH + IW)
+    OH, OW = conv1_out(IH, IW)
+    return {"x": torch.rand(N, 3, IH, IW, generator=g) - 0.3, "w": torch.randn(32, 3, 3, 3, generator=g) / 5,
+            "dy": torch.randn(N, OH, OW, 32, generator=g), "OH": OH, "OW": OW}
+
+
+def conv1_wgrad_groups(N, IH, IW, bf16_dy):
+    """(tiles, workgroups) of the weight-gradient kernel: the row kernel walks N OH one-row tiles, the tile kernel
+    N ceil(OH / 2) two-row tiles, with min(N ceil(OH / 2), 1024) workgroups either way (xcp_conv1_wgrad_parts)"""
+    OH, _ = conv1_out(IH, IW)
+    G = min(N * ((OH + 1) // 2), 1024)
+    return (N * OH if conv1_path(bf16_dy, IW, True) == "row" else N * ((OH + 1) // 2)), G
+
+
+def sparse_rows_gradient(dy, tiles, G, max_pixels=1000):
+    """The fp32-sum bound is sharp only while n^2 2^-24 << 1, so a frame batch of more than ~1100 output pixels
+    gets a gradient that is zero except at the first and last pixel of the first and last tile a workgroup
+    walks (tiles b and b + k G), for every step-th workgroup and the last one: <= max_pixels pixels.
+    dy [N,OH,OW,32]; a tile is tiles-th of the N OH OW pixels in order."""
+    N, OH, OW, C = dy.shape
+    per = N * OH * OW // tiles                       # pixels per tile (the sparse shapes have even OH)
+    step = max(1, -(-4 * G // max_pixels))
+    keep = torch.zeros(N * OH * OW, dtype=torch.bool)
+    for b in sorted(set(range(0, G, step)) | {G - 1}):
+        for t in (b, b + (tiles - 1 - b) // G * G):
+            keep[t * per] = keep[t * per + per - 1] = True
+    return dy * keep.view(N, OH, OW, 1)
+
+
+# the cases: (N, IH, IW)
+CONV1_ROW_SHAPES = [(2, 9, 4),       # OW = 1
+                    (3, 11, 35),     # OW = 17: one 16-pixel group + 1
+                    (2, 12, 13),     # even sizes: the last row and column are covered by no window
+                    (1, 5, 299),     # bench width
+                    (1, 7, 320),     # widest: three chunks per thread
+                    (70, 33, 9)]     # N OH = 1120 > 1024 workgroups: 96 walk two tiles, the prefetch clamped at T - 1
+CONV1_FWD_OTHER = [("bf16", (1, 9, 331)), ("bf16", (2, 5, 3)), ("bf16", (1, 5, CONV1_TILE_WIDEST)),   # tile kernel
+                   ("fp32", (2, 12, 13)), ("fp32", (1, 19, 75)),       # OH = 9: the last 4-row tile holds one row
+                   ("bf16", (1, 5, 700)), ("fp32", (1, 5, 700))]       # per-pixel kernel
+CONV1_WGRAD_SHAPES = [(5, 17, 23), (2, 12, 13), (1, 7, 320), (1, 9, 331), (1, 5, 700), (2, 5, 3), (2, 9, 4)]
+CONV1_WGRAD_SPARSE = (70, 33, 9)
+
+
+# ------------------------------------------------------------------ stem conv2 (csrc/conv3.hip) gradients
+def conv3x3_dgrad_ref(dy, w):
+    """dy [N,OH,OW,64], w [64,32,3,3] -> (ref64, abs_terms) [N,OH+2,OW+2,32]: the valid 3x3 conv of the pad-2
+    gradient with the flipped, transposed kernel, 9 * 64 = 576 terms (border pixels see 1 to 6 taps, the rest
+    of their terms are exact zeros)"""
+    p = F.pad(dy.double(), (0, 0, 2, 2, 2, 2))
+    ref, ab, _ = conv3x3_valid_ref(p, w.double().permute(1, 0, 2, 3).flip(2, 3))
+    return ref, ab
+
+
+def conv3x3_wgrad_ref(dy, a, flip=None):
+    """dy [N,OH,OW,64], a fp64 [N,IH,IW,32] -> (dW [64][9][32], abs_terms, extra), n = N OH OW:
+    dW[co][tap][ci] = sum_p dy[p][co] a[p + off(tap)][ci]; flip: the one-ulp allowance of a, carried through |dy|"""
+    N, OH, OW, CO = dy.shape
+    g = dy.double().reshape(-1, CO).t()
+    ref, ab, ex = [], [], []
+    for ky in range(3):
+        for kx in range(3):
+            s = a[:, ky:ky + OH, kx:kx + OW].reshape(-1, a.shape[3])
+            ref.append(g @ s)
+            ab.append(g.abs() @ s.abs())
+            ex.append(g.abs() @ flip[:, ky:ky + OH, kx:kx + OW].reshape(-1, a.shape[3]) if flip is not None
+                      else torch.zeros_like(ref[-1]))
+    return torch.stack(ref, 1), torch.stack(ab, 1), torch.stack(ex, 1)
+
+
+def bn_relu_on_load(x, s, t):
+    """c3_act: a = bf16(max(fmaf(x, s, t), 0)) -> (a fp64, its tie allowance)"""
+    a32 = fma32(x, s, t).clamp_min(0)
+    return a32.bfloat16().double(), tie_flip(a32)
+
+
+def conv3_inputs(N, IH, IW, cin, seed=0):
+    g = torch.Generator().manual_seed(7919 * seed + 1009 * N + 37 * IH + IW + cin)
+    return {"x": (torch.randn(N, IH, IW, cin, generator=g) * 1.5 + 0.3).bfloat16(),
+            "w": (torch.randn(64, 32, 3, 3, generator=g) / 288 ** 0.5).bfloat16(),
+            "s": torch.rand(32, generator=g) + 0.5, "t": torch.randn(32, generator=g) * 0.3, "g": g}
+
+
+def conv3_wgrad_inputs(N, IH, IW):
+    d = conv3_inputs(N, IH, IW, 32)
+    d["dy"] = torch.randn(N, IH - 2, IW - 2, 64, generator=d["g"]).bfloat16()
+    return d
+
+
+CONV3_DGRAD_SHAPES = [(3, 3, 3), (2, 7, 17), (3, 19, 36), (1, 4, 145), (1, 3, 147)]    # the gradient's (N, OH, OW)
+CONV3_WGRAD_SHAPES = [(3, 3, 3), (1, 6, 147), (2, 12, 34), (1, 5, 160), (1, 40, 34)]   # the input's (N, IH, IW)
+
+
+# ------------------------------------------------------------------ BN statistics (csrc/bn.hip)
+def chan_sums_ref(mode, a, b=None, mean=None, invstd=None, ms=None, mt=None):
+    """chanred_kernel's sums over the rows of a [rows, C] -> (ref64 [2,C], abs_terms, extra), n = rows (valid for
+    any partition into partial rows: the test sums the partial rows in fp64).
+    mode 0: (sum x, sum x^2) -- fmaf(x, x, acc): the square is exact.
+    mode 1: (sum dz, sum dz zhat), zhat = fl32(fl32(y - mu) is) restated with the same two fp32 operations, so
+            the term dz zhat is exact in fp64.
+    mode 2: dz masked by fmaf(y, ms, mt) > 0; where that sign is within rounding of undecided (fma_unsure) the
+            element's |term| goes into extra (a sum cannot exclude an element)."""
+    ad = a.double()
+    if mode == 0:
+        t = full = (ad, ad * ad)
+    else:
+        zhat = ((b.float() - mean) * invstd).double()
+        full = (ad, ad * zhat)                                   # the unmasked terms
+        keep = (fma32(b, ms, mt) > 0) if mode == 2 else torch.ones_like(ad, dtype=torch.bool)
+        t = tuple(v * keep for v in full)
+    ref = torch.stack([v.sum(0) for v in t])
+    ab = torch.stack([v.abs().sum(0) for v in t])
+    extra = torch.zeros_like(ab)
+    if mode == 2:
+        unsure = fma_unsure(b, ms, mt)
+        extra = torch.stack([(v.abs() * unsure).sum(0) for v in full])
+    return ref, ab, extra
+
+
+def chan_inputs(rows, C, dtype, seed=0):
+    """y, dz and the batch's own mean / invstd (so the dz zhat sums cancel), a ReLU affine"""
+    g = torch.Generator().manual_seed(104729 * seed + 13 * rows + C)
+    y = (torch.randn(rows, C, generator=g) * 1.3 + 0.4).to(dtype)
+    dz = torch.randn(rows, C, generator=g).to(dtype)
+    yd = y.double()
+    mean = yd.mean(0)
+    var = (yd * yd).mean(0) - mean * mean
+    return {"y": y, "dz": dz, "mean": mean.float(), "invstd": (1 / (var + 1e-5).sqrt()).float(),
+            "ms": torch.rand(C, generator=g) + 0.5, "mt": torch.randn(C, generator=g) * 0.3}
+
+
+CHAN_SHAPES = [(1083, 728), (1083, 736), (50, 2048), (5, 64), (147, 32), (1, 8), (1001, 8)]   # rows, C
+BN_STRIDED_SHAPES = [(2, 19, 20, 128), (1, 7, 5, 728), (3, 4, 4, 64)]                         # N, H, W, C
+
+FIN_ROWS = [1, 15, 16, 17, 767, 768, 769, 2048, 2049]     # 2049 > FIN_MAX_ROWS: pre-reduced by ops._fold
+FIN_CHANNELS = [(32, 32), (40, 40), (728, 736)]           # C, CP
+FIN_MAX_ROWS = 2048
+FIN_BWD_FORMS = ["plain", "accumulate", "narrow", "frozen", "narrow+accumulate"]
+U64 = 2.0 ** -53
+
+
+def _fin_sums(part, C):
+    """fp64 column sums of the fp32 partial rows part [R,2,CP] and what they may be off by: the fp64 summation
+    order, R 2^-53 sum |part|; above FIN_MAX_ROWS rows ops._fold pre-reduces them to fp32 group sums, each
+    rounded once: 2^-24 sum |part|."""
+    R = part.shape[0]
+    p = part.double()[:, :, :C]
+    s, a = p.sum(0), p.abs().sum(0)
+    noise = a * (R * U64 + (U32 if R > FIN_MAX_ROWS else 0.0))
+    return s[0], s[1], noise[0], noise[1]
+
+
+def bn_finalize_ref(part, count, gamma, beta, rmean, rvar, momentum, eps):
+    """bn_finalize_part_kernel's fp64 expression on the fp32 partial rows part [R,2,CP] (C = len(gamma)):
+        mean = s / count, var = max(q / count - mean^2, 0), is = 1 / sqrt(var + eps),
+        scale = gamma fl32(is), shift = beta - fl32(mean) scale (fp32, fma or not),
+        running = (1 - momentum) running + momentum (mean | var count / (count - 1))
+    -> {name: (ref64 [C], bound [C])}.  Each bound counts the code's own roundings: one fp32 rounding (2^-24
+    relative) for mean, invstd and the running statistics, one more for scale, 2^-24 (|beta| + 2 |mean scale|) for
+    shift plus what the errors of fl32(mean) and scale carry into it; the noise of the sums (_fin_sums) is
+    carried through var's cancellation and through 1 / sqrt by evaluating is at var -+ dvar (negligible except
+    for a constant channel)."""
+    C = gamma.shape[0]
+    s, q, ds, dq = _fin_sums(part, C)
+    gm, be = gamma.double(), beta.double()
+    mom, ep = float(torch.tensor(momentum, dtype=torch.float32)), float(torch.tensor(eps, dtype=torch.float32))
+    mean = s / count
+    dmean = ds / count + 2 * U64 * mean.abs()
+    q1 = q / count
+    var = (q1 - mean * mean).clamp_min(0)
+    dvar = dq / count + 2 * mean.abs() * dmean + 4 * U64 * (q1.abs() + mean * mean)
+    inv = 1 / (var + ep).sqrt()
+    dis = torch.maximum(1 / ((var - dvar).clamp_min(0) + ep).sqrt() - inv, inv - 1 / (var + dvar + ep).sqrt())
+    dis = dis + 4 * U64 * inv
+    e_mean = dmean + U32 * mean.abs()                       # of fl32(mean)
+    e_is = dis + U32 * inv                                  # of fl32(is)
+    scale = gm * inv
+    e_scale = gm.abs() * e_is + U32 * scale.abs()
+    shift = be - mean * scale
+    e_shift = U32 * (be.abs() + 2 * (mean * scale).abs()) + mean.abs() * e_scale + scale.abs() * e_mean
+    unb = var * count / (count - 1) if count > 1 else var
+    dunb = dvar * (count / (count - 1) if count > 1 else 1.0)
+    rm = (1 - mom) * rmean.double() + mom * mean
+    rv = (1 - mom) * rvar.double() + mom * unb
+    return {"mean": (mean, e_mean), "invstd": (inv, e_is), "scale": (scale, e_scale), "shift": (shift, e_shift),
+            "running_mean": (rm, U32 * rm.abs() + mom * dmean + 4 * U64 * (rmean.double().abs() + mean.abs())),
+            "running_var": (rv, U32 * rv.abs() + mom * dunb + 4 * U64 * (rvar.double().abs() + unb.abs()))}
+
+
+def bn_eval_ref(gamma, beta, rmean, rvar, eps):
+    """xcp_bn_finalize with train = 0: mean = running_mean, var = running_var (both fp32 already)"""
+    gm, be, mean = gamma.double(), beta.double(), rmean.double()
+    ep = float(torch.tensor(eps, dtype=torch.float32))
+    inv = 1 / (rvar.double() + ep).sqrt()
+    e_is = (U32 + 4 * U64) * inv
+    scale = gm * inv
+    e_scale = gm.abs() * e_is + U32 * scale.abs()
+    shift = be - mean * scale
+    return {"mean": (mean, torch.zeros_like(mean)), "invstd": (inv, e_is), "scale": (scale, e_scale),
+            "shift": (shift, U32 * (be.abs() + 2 * (mean * scale).abs()) + mean.abs() * e_scale)}
+
+
+def bn_bwd_finalize_ref(part, count, gamma, mean, invstd, frozen=False, base=None):
+    """bn_bwd_finalize_part_kernel's fp64 expression on the fp32 partial rows (sum dz, sum dz zhat):
+        a = gamma is, alpha = fl32(a), bcoef = fl32(-a is mdzy), delta = fl32(-a mdz + a is mu mdzy)
+        (mdz = sdz / count, ...; frozen: bcoef = delta = 0 exactly), dgamma = fl32(sdzy), dbeta = fl32(sdz);
+        base = (dgamma0, dbeta0): the accumulate form adds them in fp32 (one more rounding).
+    -> {name: (ref64 [C], bound [C])}: one fp32 rounding each, plus the sums' noise (_fin_sums) through the
+    expression, plus fp64's own rounding of delta's cancellation."""
+    C = gamma.shape[0]
+    sdz, sdzy, ds, dq = _fin_sums(part, C)
+    inv, gm, mu = invstd.double()[:C], gamma.double(), mean.double()[:C]
+    a = gm * inv
+    mdz, mdzy = sdz / count, sdzy / count
+    z = torch.zeros_like(a)
+    bc = -a * inv * mdzy
+    t1, t2 = -a * mdz, a * inv * mu * mdzy
+    e_bc = U32 * bc.abs() + (a * inv).abs() * dq / count + 4 * U64 * bc.abs()
+    e_de = U32 * (t1 + t2).abs() + a.abs() * ds / count + (a * inv * mu).abs() * dq / count \
+        + 6 * U64 * (t1.abs() + t2.abs())
+    out = {"alpha": (a, U32 * a.abs()), "bcoef": (z, z) if frozen else (bc, e_bc),
+           "delta": (z, z) if frozen else (t1 + t2, e_de)}
+    for name, sm, dn, b0 in (("dgamma", sdzy, dq, None if base is None else base[0]),
+                             ("dbeta", sdz, ds, None if base is None else base[1])):
+        ref, e = sm, U32 * sm.abs() + dn
+        if b0 is not None:
+            ref, e = sm + b0.double()[:C], e + U32 * (sm.abs() + b0.double()[:C].abs())
+        out[name] = (ref, e)
+    return out
+
+
+def assert_within(got, ref64, bound, tag=""):
+    """|got - ref64| <= bound per element, through assert_f32_sum (no terms, the bound as `extra`)"""
+    return assert_f32_sum(got, ref64, torch.zeros_like(ref64), 0, extra=bound, tag=tag)
+
+
+def fin_fwd_inputs(R, C, CP, seed=0):
+    """Partial rows written as fp32 sums of two data rows each (count = 2 R, q consistent with s), with, among the
+    channels: 0 all zero, 1 constant 3.0 (var exactly 0: the sums are small integers), 2 with |mean| = 50 std;
+    gamma, beta and non-trivial running statistics.  The padding channels of part hold junk the kernel must not
+    use."""
+    g = torch.Generator().manual_seed(15485863 * seed + 31 * R + C)
+    x = torch.randn(R, 2, C, generator=g) * (torch.rand(C, generator=g) + 0.5) + torch.randn(C, generator=g)
+    x[:, :, 0] = 0.0
+    x[:, :, 1] = 3.0
+    x[:, :, 2] = 50.0 + torch.randn(R, 2, generator=g)
+    part = torch.randn(R, 2, CP, generator=g)
+    part[:, 0, :C] = x[:, 0] + x[:, 1]
+    part[:, 1, :C] = x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1]
+    return {"part": part, "count": 2 * R, "gamma": torch.rand(C, generator=g) + 0.5, "beta": torch.randn(C, generator=g),
+            "rmean": torch.randn(C, generator=g) * 0.3, "rvar": torch.rand(C, generator=g) + 0.5, "momentum": 0.1,
+            "eps": 1e-5}
+
+
+def fin_bwd_inputs(R, C, CP, seed=0):
+    """gradient partial rows of realistic size (1e-3), statistics with the three special channels of
+    fin_fwd_inputs (zero: invstd = 1 / sqrt(eps); constant; |mean| = 50 std), earlier dgamma / dbeta"""
+    g = torch.Generator().manual_seed(32452843 * seed + 17 * R + C)
+    part = torch.randn(R, 2, CP, generator=g) * 1e-3
+    mean, invstd = torch.randn(CP, generator=g), 1 / (torch.rand(CP, generator=g) + 0.3)
+    mean[0], invstd[0] = 0.0, float(1 / torch.tensor(1e-5, dtype=torch.float64).sqrt())
+    mean[1], invstd[1] = 3.0, invstd[0]
+    mean[2], invstd[2] = 50.0, 1.0
+    return {"part": part, "count": 2 * R, "gamma": torch.rand(C, generator=g) + 0.5, "mean": mean, "invstd": invstd,
+            "dgamma0": torch.randn(C, generator=g), "dbeta0": torch.randn(C, generator=g)}

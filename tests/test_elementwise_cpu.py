@@ -7,6 +7,11 @@ kernels (the inputs are generated on the CPU), with the excluded share <= 1e-4 a
 share >= 0.99.  The nine-slice pool references are checked against torch's own pooling.
 
 Sharp: planted defects that the norm measure of test_gpu_kernels.py lets through make it raise.
+
+The second half does the same for the stem convolutions and the BatchNorm statistics chain
+(test_gpu_elementwise_stem_bn.py): the split-bf16 allowance of the conv1 row kernels is shown to be enough by
+an emulation that forms hi / lo with .bfloat16() and adds the product groups in fp32; the finalize bounds by
+the kernels' fp64 expression with the partial rows summed in another order and the outputs cast to fp32.
 """
 import pytest
 import torch
@@ -256,3 +261,390 @@ def test_maxpool_first_max_rule():
     z[0, 1, 1, 0] = z[0, 2, 2, 0] = 5.0      # window (1, 1) holds both: taps 0 and 4, the first wins
     m, am = E.maxpool3s2_ref(z)
     assert am[0, :, :, 0].tolist() == [[8, 6], [2, 0]] and (m == 5).all()
+
+
+# ================================================================== stem convs and BN statistics
+BF, FP = torch.bfloat16, torch.float32
+
+
+def split(v):
+    """bf16 head and tail of an fp32 tensor, as fp32 (v - hi is exact in fp32)"""
+    hi = v.bfloat16().float()
+    return hi, (v - hi).bfloat16().float()
+
+
+def patches(x):
+    """[N, 27, OH OW] fp32 im2col of the 3x3 stride-2 valid conv, k = ci 9 + ky 3 + kx"""
+    return F.unfold(x, 3, stride=2)
+
+
+def emu_conv1_fwd(x, w, path, order, dtype):
+    """27 fp32 products per output added one by one (k ascending or descending); path "row": the products are
+    the three groups lo.hi, hi.lo, hi.hi of the split operands (bf16 x bf16 is exact in fp32)"""
+    P, w2 = patches(x), w.reshape(32, 27)
+    N, _, L = P.shape
+    ks = list(range(27)) if order == 0 else list(range(26, -1, -1))
+    groups = [(P, w2)]
+    if path == "row":
+        (ph, pl), (wh, wl) = split(P), split(w2)
+        groups = [(pl, wh), (ph, wl), (ph, wh)]
+        if order:
+            groups.reverse()
+    acc = torch.zeros(N, L, 32)
+    for a, b in groups:
+        for k in ks:
+            acc = acc + a[:, k, :, None] * b[:, k]
+    OH, OW = E.conv1_out(x.shape[2], x.shape[3])
+    return acc.view(N, OH, OW, 32).to(dtype)
+
+
+def emu_conv1_wgrad(x, dy, path, order):
+    """dW[co][k] = sum_p dy[p][co] patch[p][k] in fp32, the pixels in two orders (forward in one product;
+    reversed and in two halves); path "row": X split into head and tail, two product groups"""
+    P = patches(x).permute(0, 2, 1).reshape(-1, 27)
+    g = dy.float().reshape(-1, 32)
+    if order:
+        P, g = P.flip(0), g.flip(0)
+    parts = split(P)[::-1] if path == "row" else (P,)
+    h = P.shape[0] // 2
+    acc = torch.zeros(32, 27)
+    for a in parts:
+        acc = acc + (g.t() @ a if order == 0 else (g[h:].t() @ a[h:] + g[:h].t() @ a[:h]))
+    return acc.view(32, 3, 3, 3)
+
+
+def conv1_fwd_cases():
+    return [("bf16", s) for s in E.CONV1_ROW_SHAPES] + E.CONV1_FWD_OTHER
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("dt,shape", conv1_fwd_cases(), ids=str)
+def test_sound_conv1_fwd(dt, shape, order):
+    d = E.conv1_inputs(*shape)
+    path = E.conv1_path(dt == "bf16", shape[2])
+    ref, ab, extra = E.conv1_ref(d["x"], d["w"], split=path == "row")
+    out = emu_conv1_fwd(d["x"], d["w"], path, order, BF if dt == "bf16" else FP)
+    if dt == "bf16":
+        assert E.assert_bf16_stored(out, ref, ab, 27, extra=extra)["nearest"] >= 0.99
+    else:
+        E.assert_f32_sum(out, ref, ab, 27)
+
+
+def test_conv1_paths():
+    """the kernel each shape list is meant for, restated from the launchers"""
+    assert all(E.conv1_path(True, s[2]) == "row" for s in E.CONV1_ROW_SHAPES)
+    assert [E.conv1_path(dt == "bf16", s[2]) for dt, s in E.CONV1_FWD_OTHER] == ["tile"] * 5 + ["pixel"] * 2
+    assert E.conv1_path(True, 3) == "tile" and E.conv1_path(True, E.CONV1_TILE_WIDEST + 1) == "pixel"
+    assert [E.conv1_path(True, s[2], True) for s in E.CONV1_WGRAD_SHAPES] == \
+        ["row", "row", "row", "tile", "pixel", "tile", "row"]
+    assert [E.conv1_path(False, s[2], True) for s in E.CONV1_WGRAD_SHAPES] == \
+        ["tile", "tile", "tile", "tile", "pixel", "tile", "tile"]
+
+
+def test_conv1_wgrad_ref_is_the_sum_over_pixels():
+    """conv2d_weight with stride 2 on an even-sized frame (uncovered last row / column) against the im2col sum"""
+    d = E.conv1_inputs(2, 12, 13)
+    ref, ab, _, n = E.conv1_wgrad_ref(d["x"], d["dy"])
+    P = patches(d["x"].double()).permute(0, 2, 1).reshape(-1, 27)
+    torch.testing.assert_close(ref.reshape(32, 27), d["dy"].double().reshape(-1, 32).t() @ P, rtol=0, atol=1e-12)
+    assert n == 2 * 5 * 6 and (ab >= ref.abs() - 1e-12).all()
+
+
+def wgrad_case(shape, dt, sparse=False):
+    d = E.conv1_inputs(*shape)
+    dy = d["dy"].to(BF if dt == "bf16" else FP)
+    if sparse:
+        dy = E.sparse_rows_gradient(dy, *E.conv1_wgrad_groups(*shape, dt == "bf16"))
+    return d, dy, E.conv1_path(dt == "bf16", shape[2], True)
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("dt", ["bf16", "fp32"])
+@pytest.mark.parametrize("shape", E.CONV1_WGRAD_SHAPES + [E.CONV1_WGRAD_SPARSE], ids=str)
+def test_sound_conv1_wgrad(shape, dt, order):
+    d, dy, path = wgrad_case(shape, dt, shape == E.CONV1_WGRAD_SPARSE)
+    ref, ab, extra, n = E.conv1_wgrad_ref(d["x"], dy, split=path == "row")
+    assert n <= 1100
+    E.assert_f32_sum(emu_conv1_wgrad(d["x"], dy, path, order), ref, ab, n, extra=extra)
+
+
+def test_sparse_gradient_covers_the_tile_edges():
+    shape = E.CONV1_WGRAD_SPARSE
+    tiles, G = E.conv1_wgrad_groups(*shape, True)
+    assert (tiles, G) == (1120, 560)
+    dy = E.sparse_rows_gradient(E.conv1_inputs(*shape)["dy"], tiles, G)
+    nz = (dy != 0).any(-1).view(tiles, -1)               # [tile][ow]
+    assert nz.sum() <= 1000
+    for b in (0, G - 1):                                  # first and last workgroup: tiles b and b + G
+        assert nz[b, 0] and nz[b, -1] and nz[b + G, 0] and nz[b + G, -1]
+
+
+def emu_conv3_dgrad(dy, w, order):
+    p = F.pad(dy.float(), (0, 0, 2, 2, 2, 2))
+    wf = w.float().permute(1, 0, 2, 3).flip(2, 3)
+    N, H, W, _ = p.shape
+    acc = torch.zeros(N, H - 2, W - 2, 32)
+    for t in (range(9) if order == 0 else range(8, -1, -1)):
+        ky, kx = divmod(t, 3)
+        acc = acc + p[:, ky:ky + H - 2, kx:kx + W - 2] @ wf[:, :, ky, kx].t()
+    return acc.bfloat16()
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("shape", E.CONV3_DGRAD_SHAPES, ids=str)
+def test_sound_conv3x3_dgrad(shape, order):
+    d = E.conv3_inputs(*shape, 64)
+    ref, ab = E.conv3x3_dgrad_ref(d["x"], d["w"])
+    assert ref.shape[1:3] == (shape[1] + 2, shape[2] + 2)
+    assert E.assert_bf16_stored(emu_conv3_dgrad(d["x"], d["w"], order), ref, ab, 576)["nearest"] >= 0.99
+    # against autograd's input gradient
+    want = torch.nn.grad.conv2d_input((shape[0], 32, shape[1] + 2, shape[2] + 2), d["w"].double(),
+                                      d["x"].double().permute(0, 3, 1, 2))
+    torch.testing.assert_close(ref.permute(0, 3, 1, 2), want, rtol=0, atol=1e-12)
+
+
+def conv3_wgrad_case(shape, bn):
+    d = E.conv3_wgrad_inputs(*shape)
+    dy = d["dy"]
+    a, flip = E.bn_relu_on_load(d["x"], d["s"], d["t"]) if bn else (d["x"].double(), None)
+    return d, dy, a, flip
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("bn", [False, True])
+@pytest.mark.parametrize("shape", E.CONV3_WGRAD_SHAPES, ids=str)
+def test_sound_conv3x3_wgrad(shape, bn, order):
+    d, dy, a, flip = conv3_wgrad_case(shape, bn)
+    ref, ab, extra = E.conv3x3_wgrad_ref(dy, a, flip)
+    N, OH, OW, _ = dy.shape
+    g, a32 = dy.float().reshape(-1, 64), a.float()
+    if order:
+        g = g.flip(0)
+    out = torch.stack([g.t() @ (s.flip(0) if order else s) for s in
+                       (a32[:, ky:ky + OH, kx:kx + OW].reshape(-1, 32) for ky in range(3) for kx in range(3))], 1)
+    E.assert_f32_sum(out, ref, ab, N * OH * OW, extra=extra)
+    want = torch.nn.grad.conv2d_weight(a.permute(0, 3, 1, 2), (64, 32, 3, 3), dy.double().permute(0, 3, 1, 2))
+    torch.testing.assert_close(ref.view(64, 3, 3, 32).permute(0, 3, 1, 2), want, rtol=0, atol=1e-10)
+
+
+def emu_chan_sums(mode, d, order):
+    y, dz = d["y"].float(), d["dz"].float()
+    if mode == 0:
+        t = (y, y * y)
+    else:
+        if mode == 2:
+            dz = dz * (E.fma32(d["y"], d["ms"], d["mt"]) > 0)
+        t = (dz, dz * ((y - d["mean"]) * d["invstd"]))
+    if order == 0:
+        return torch.stack([v.sum(0) for v in t])
+    return torch.stack([sum(v.flip(0)[i::5].sum(0) for i in range(5)) for v in t])
+
+
+def chan_ref(mode, d):
+    if mode == 0:
+        return E.chan_sums_ref(0, d["y"])
+    return E.chan_sums_ref(mode, d["dz"], d["y"], d["mean"], d["invstd"], d["ms"], d["mt"])
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("dt", [BF, FP], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("shape", E.CHAN_SHAPES, ids=str)
+def test_sound_chan_sums(shape, dt, mode, order):
+    d = E.chan_inputs(*shape, dt)
+    ref, ab, extra = chan_ref(mode, d)
+    E.assert_f32_sum(emu_chan_sums(mode, d, order), ref, ab, shape[0], extra=extra)
+
+
+def wave_sums(part, C, nw=16):
+    """column sums in the order of fin_reduce: rows w, w + nw, ... per wave, then the waves; more than
+    FIN_MAX_ROWS rows are first folded to 256 fp32 group sums (ops._fold)"""
+    p = part[:, :, :C]
+    if p.shape[0] > E.FIN_MAX_ROWS:
+        R = p.shape[0]
+        grp = torch.arange(R) * 256 // R
+        p = torch.stack([p[grp == i].double().sum(0).float() for i in range(256)])
+    p = p.double()
+    s = sum(p[w::nw].flip(0).sum(0) for w in range(min(nw, p.shape[0])))
+    return s[0], s[1]
+
+
+def emu_bn_finalize(d, swap_mean=None):
+    C = d["gamma"].shape[0]
+    s, q = wave_sums(d["part"], C)
+    mom, eps = float(torch.tensor(d["momentum"], dtype=FP)), float(torch.tensor(d["eps"], dtype=FP))
+    mean = s / d["count"]
+    var = (q / d["count"] - mean * mean).clamp_min(0)
+    unb = var * d["count"] / (d["count"] - 1) if d["count"] > 1 else var
+    inv = (1 / (var + eps).sqrt()).float()
+    sc = d["gamma"] * inv
+    m32 = mean.float()
+    if swap_mean is not None:      # the planted defect: channel c's shift from channel c + 1's mean
+        m32 = m32.clone()
+        m32[swap_mean] = mean.float()[swap_mean + 1]
+    return {"mean": mean.float(), "invstd": inv, "scale": sc, "shift": d["beta"] - m32 * sc,
+            "running_mean": ((1 - mom) * d["rmean"].double() + mom * mean).float(),
+            "running_var": ((1 - mom) * d["rvar"].double() + mom * unb).float()}
+
+
+def emu_bn_bwd_finalize(d, form, nw=16):
+    C = d["gamma"].shape[0]
+    sdz, sdzy = wave_sums(d["part"], C, nw)
+    inv, gm, mu = d["invstd"].double()[:C], d["gamma"].double(), d["mean"].double()[:C]
+    a = gm * inv
+    mdz, mdzy = sdz / d["count"], sdzy / d["count"]
+    z = torch.zeros(C)
+    fro, acc = "frozen" in form, "accumulate" in form
+    return {"alpha": a.float(), "bcoef": z if fro else (-a * inv * mdzy).float(),
+            "delta": z if fro else (-a * mdz + a * inv * mu * mdzy).float(),
+            "dgamma": d["dgamma0"] + sdzy.float() if acc else sdzy.float(),
+            "dbeta": d["dbeta0"] + sdz.float() if acc else sdz.float()}
+
+
+def fin_ref(d):
+    return E.bn_finalize_ref(d["part"], d["count"], d["gamma"], d["beta"], d["rmean"], d["rvar"], d["momentum"],
+                             d["eps"])
+
+
+def fin_bwd_ref(d, form):
+    base = (d["dgamma0"], d["dbeta0"]) if "accumulate" in form else None
+    return E.bn_bwd_finalize_ref(d["part"], d["count"], d["gamma"], d["mean"], d["invstd"], "frozen" in form, base)
+
+
+@pytest.mark.parametrize("C,CP", E.FIN_CHANNELS)
+@pytest.mark.parametrize("R", E.FIN_ROWS)
+def test_sound_bn_finalize(R, C, CP):
+    d = E.fin_fwd_inputs(R, C, CP)
+    ref, out = fin_ref(d), emu_bn_finalize(d)
+    for k, (r, b) in ref.items():
+        E.assert_within(out[k], r, b, tag=k)
+    # the constant channel: var is exactly zero, whatever the order of the sums
+    assert ref["invstd"][0][1].float() == (1 / torch.tensor(1e-5, dtype=FP).double().sqrt()).float()
+    assert out["mean"][1] == 3.0 and out["invstd"][1] == out["invstd"][0]
+
+
+@pytest.mark.parametrize("form", E.FIN_BWD_FORMS)
+@pytest.mark.parametrize("C,CP", E.FIN_CHANNELS)
+@pytest.mark.parametrize("R", E.FIN_ROWS)
+def test_sound_bn_bwd_finalize(R, C, CP, form):
+    d = E.fin_bwd_inputs(R, C, CP)
+    out = emu_bn_bwd_finalize(d, form, 4 if "narrow" in form else 16)
+    for k, (r, b) in fin_bwd_ref(d, form).items():
+        E.assert_within(out[k], r, b, tag=k)
+
+
+# ------------------------------------------------------------------ sharp: stem and statistics
+@pytest.fixture(scope="module")
+def conv1_case():
+    """the bench frame of test_conv1_fwd_wgrad (2 x 299 x 299, bf16: the row kernel)"""
+    d = E.conv1_inputs(2, 299, 299)
+    ref, ab, extra = E.conv1_ref(d["x"], d["w"], split=True)
+    out = emu_conv1_fwd(d["x"], d["w"], "row", 0, BF)
+    E.assert_bf16_stored(out, ref, ab, 27, extra=extra)
+    return d, ref, ab, extra, out
+
+
+def test_sharp_conv1_tap_dropped_at_one_pixel(conv1_case):
+    d, ref, ab, extra, out = conv1_case
+    bad = out.clone()
+    n, oh, ow, k = 1, 148, 0, 26                    # tap (ci, ky, kx) = (2, 2, 2) of the first pixel of the last row
+    xv = d["x"][n, 2, 2 * oh + 2, 2 * ow + 2]
+    bad[n, oh, ow] = (out[n, oh, ow].float() - xv * d["w"].reshape(32, 27)[:, k]).bfloat16()
+    caught(bad, ref, ab, 27, extra)
+
+
+def test_sharp_conv1_last_column_from_the_clamped_row(conv1_case):
+    """pixel OW - 1 of one row stored from A row OW - 2"""
+    d, ref, ab, extra, out = conv1_case
+    bad = out.clone()
+    bad[0, 77, 148] = out[0, 77, 147]
+    caught(bad, ref, ab, 27, extra)
+
+
+def test_sharp_conv1_wgrad_pixel_dropped():
+    """One pixel (the last of a workgroup's last tile) missing from one output channel's sum, at the sparse
+    gradient's 752 nonzero pixels: rel_err < 1e-2 over dW passes, the fp32-sum bound does not."""
+    d, dy, path = wgrad_case(E.CONV1_WGRAD_SPARSE, "bf16", True)
+    ref, ab, extra, n = E.conv1_wgrad_ref(d["x"], dy, split=True)
+    out = emu_conv1_wgrad(d["x"], dy, path, 0)
+    E.assert_f32_sum(out, ref, ab, n, extra=extra)
+    N, OH, OW, _ = dy.shape
+    P = patches(d["x"]).permute(0, 2, 1).reshape(-1, 27)
+    p = N * OH * OW - 1
+    co = int((dy.reshape(-1, 32)[p].float().abs() - 0.5).abs().argmin())      # a gradient of middling size
+    assert 0.25 < dy.reshape(-1, 32)[p, co].abs() < 1
+    bad = out.clone()
+    bad[co] -= (dy.reshape(-1, 32)[p, co].float() * P[p]).view(3, 3, 3)
+    assert rel_err(bad, ref) < 1e-2
+    with pytest.raises(AssertionError, match="outside the fp32 bound"):
+        E.assert_f32_sum(bad, ref, ab, n, extra=extra)
+
+
+def test_sharp_row_dropped_from_the_gradient_sums():
+    """chanred (bn_bwd_reduce) without the last row of a ragged chunk, at a gradient of realistic size: dbeta /
+    dgamma move by less than test_bn_forward_backward's atol 1e-3, and leave the fp32-sum bound."""
+    rows, C = 1083, 728
+    d = E.chan_inputs(rows, C, BF)
+    d["dz"] = (d["dz"].float() * 1e-4).bfloat16()
+    ref, ab, extra = chan_ref(1, d)
+    out = emu_chan_sums(1, d, 0)
+    E.assert_f32_sum(out, ref, ab, rows, extra=extra)
+    short = dict(d, y=d["y"][:-1], dz=d["dz"][:-1])
+    bad = emu_chan_sums(1, short, 0)
+    torch.testing.assert_close(bad.double(), ref, rtol=1e-4, atol=1e-3)
+    with pytest.raises(AssertionError, match="outside the fp32 bound"):
+        E.assert_f32_sum(bad, ref, ab, rows, extra=extra)
+
+
+def test_sharp_row_dropped_from_row_stats():
+    """row_stats without its last row: the normalised bf16 output it leads to passes rel_err < 1e-2 (the bf16
+    measure of test_bn_forward_backward), the sums leave the bound."""
+    rows, C = 1083, 728
+    d = E.chan_inputs(rows, C, BF)
+    ref, ab, extra = chan_ref(0, d)
+    bad = emu_chan_sums(0, dict(d, y=d["y"][:-1]), 0)
+
+    def normalised(s):
+        mean = s[0] / rows
+        inv = 1 / (s[1] / rows - mean * mean + 1e-5).sqrt()
+        return ((d["y"].double() - mean) * inv).bfloat16()
+
+    assert rel_err(normalised(bad.double()).float(), normalised(ref)) < 1e-2
+    with pytest.raises(AssertionError, match="outside the fp32 bound"):
+        E.assert_f32_sum(bad, ref, ab, rows, extra=extra)
+
+
+def test_sharp_last_partial_row_left_out_of_a_finalize():
+    """R = 769: one row past the 16 x 48 rows of fin_reduce's first pass.  Without it dgamma / dbeta and the
+    coefficients stay within rtol 1e-4 / atol 1e-3 and leave their bounds."""
+    d = E.fin_bwd_inputs(769, 728, 736)
+    d["part"] = d["part"] * 0.1                      # partial sums of 1e-4: one row moves a sum by << 1e-3
+    ref = fin_bwd_ref(d, "plain")
+    bad = emu_bn_bwd_finalize(dict(d, part=d["part"][:-1]), "plain")
+    for k in ("dgamma", "dbeta", "bcoef", "delta"):          # (channels 3 ..: invstd of ordinary size)
+        r, b = ref[k]
+        torch.testing.assert_close(bad[k][3:].double(), r[3:], rtol=1e-4, atol=1e-3)
+        with pytest.raises(AssertionError, match="outside the fp32 bound"):
+            E.assert_within(bad[k][3:], r[3:], b[3:], tag=k)
+    # the forward finalize, the last two data rows small (0.01) in the ordinary channels 3 ..
+    f = E.fin_fwd_inputs(769, 40, 40)
+    f["part"][-1, 0, 3:], f["part"][-1, 1, 3:] = 2 * 0.01, 2 * 0.01 ** 2
+    rf = fin_ref(f)
+    badf = emu_bn_finalize(dict(f, part=f["part"][:-1]))
+    for k in ("mean", "shift"):
+        r, b = rf[k]
+        torch.testing.assert_close(badf[k][3:].double(), r[3:], rtol=1e-4, atol=1e-3)
+        with pytest.raises(AssertionError, match="outside the fp32 bound"):
+            E.assert_within(badf[k][3:], r[3:], b[3:], tag=k)
+
+
+def test_sharp_shift_from_the_neighbouring_channels_mean():
+    """shift[c] formed with channel c + 1's mean, the two means 5e-4 apart: inside atol 1e-3, outside the bound"""
+    d = E.fin_fwd_inputs(17, 40, 40)
+    c = 7
+    d["part"][:, 0, c + 1] = d["part"][:, 0, c] + 1e-3          # two data rows per partial row
+    ref = fin_ref(d)
+    bad = emu_bn_finalize(d, swap_mean=c)
+    torch.testing.assert_close(bad["shift"].double(), ref["shift"][0], rtol=1e-4, atol=1e-3)
+    with pytest.raises(AssertionError, match="outside the fp32 bound"):
+        E.assert_within(bad["shift"], *ref["shift"], tag="shift")
