@@ -243,6 +243,24 @@ int xcp_frames_u8_to_f32(const unsigned char* in, const int* len, float* out, in
 int xcp_frames_prep(const unsigned char* in, const int* len, void* out, int B, int Tmax, int H, int W, int OH, int OW,
                     int dtype, int nhwc, xcp_stream_t stream);
 
+/* ---- clip augmentation (train_au_patch.py:193 augment_train, Xception.py:12-17 mean / std 0.5) ----
+ * in, len as above; tab [B][XCP_AUG_COLS] int32 (device), one row per clip, shared by its frames:
+ *   0 t0, 1 tstride, 2 y0, 3 x0, 4 bh, 5 bw, 6 flip, 7 ey0, 8 ex0, 9 eh, 10 ew, 11 unused,
+ *   12-14 a[3], 15-17 b[3], 18-20 fill[3] (fp32 bit patterns), 21-23 unused.
+ * out [B][Tout][3][OH][OW] (nhwc 1: [B][Tout][OH][OW][3]) of dtype, out_len [B] int32 (device):
+ *   out_len[b] = min(Tout, max(0, ceil((clamp(len[b], 0, Tmax) - t0) / tstride))); output frame
+ *   t < out_len[b] is source frame t0 + t * tstride: x / 255, the crop box (y0, x0, bh, bw)
+ *   resampled bilinearly (align_corners=False) to OH x OW, flipped left-right if flip, then
+ *   v * a[c], then + b[c] (two roundings), fill[c] inside the erase rectangle (ey0, ex0, eh, ew:
+ *   output coordinates, clipped to the output, empty when eh or ew is 0), cast (bf16: nearest
+ *   even); frames t >= out_len[b] are zero.  The kernel clamps t0 to [0, Tmax], tstride to
+ *   [1, Tmax], bh to [1, H], bw to [1, W], y0 to [0, H - bh], x0 to [0, W - bw]: no table reads or
+ *   writes out of bounds.  No host read, no allocation: a call can be captured in a graph and
+ *   replayed after tab has been rewritten in place. */
+#define XCP_AUG_COLS 24
+int xcp_clip_augment(const unsigned char* in, const int* len, const int* tab, void* out, int* out_len, int B, int Tmax,
+                     int Tout, int H, int W, int OH, int OW, int dtype, int nhwc, xcp_stream_t stream);
+
 /* ---- audio front end (XceptionLSTMA.py:44-46): F.interpolate(bilinear, align_corners=False) ----
  * out [NC][OH][OW] fp32 = bilinear resize of in [NC][IH][IW] fp32 (ATen's source-index and
  * weight formulas in fp32); MFCC frames [B*T*3][13][1] -> [B*T*3][64][64] */

@@ -98,16 +98,32 @@ class PinnedClipReader:
 
     Iterating yields ``(clips [B, Tmax, 3, OH, OW], labels [B, 1] fp32, lengths [B] int32)`` on
     the device, clips equal to ``collate_fn`` of FaceDataset items (then resized / cast).
+
+    ``augment``: an ``xcp.augment.ClipAugment``.  The reader thread then draws the batch's
+    parameter table (``augment_table``: seeded by (seed, epoch, batch index), so it does not
+    depend on thread timing), the table travels with the batch on the copy stream, and
+    ``xcp_clip_augment`` takes the place of ``xcp_frames_prep``: clips are
+    ``[B, augment.frames or Tmax, 3, *augment.size]`` and the yielded lengths are the
+    augmented clips' (frame sub-sampling shortens them).
     """
 
     def __init__(self, folder_path, batch_size, device, size=None, dtype=torch.float32, channels_last=False,
-                 shuffle=False, seed=0, drop_last=False):
+                 shuffle=False, seed=0, drop_last=False, augment=None):
         self.files = FaceDataset(folder_path).npy_files
         self.batch_size = batch_size
         self.device = torch.device(device)
         self.size, self.dtype, self.channels_last = size, dtype, channels_last
         self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
         self.epoch = 0
+        self.augment = augment
+        if augment is not None and size is not None and tuple(size) != tuple(augment.size):
+            raise ValueError(f"size {tuple(size)} contradicts augment.size {tuple(augment.size)}")
+
+    def augment_table(self, epoch, index, lengths, H, W):
+        """The AugmentParams of batch ``index`` of epoch ``epoch``: a function of (seed, epoch,
+        index) and the batch's clip lengths and frame size only."""
+        rng = np.random.default_rng([self.seed, epoch, index])
+        return self.augment.sample(lengths.tolist(), H, W, rng)
 
     def __len__(self):
         n = len(self.files)
@@ -153,9 +169,14 @@ class PinnedClipReader:
         import threading
         from xcp import ops
         batches = self.batches()
+        epoch, aug = self.epoch, self.augment
         self.epoch += 1
         copy_stream = torch.cuda.Stream(self.device)
         bufs = [None, None]
+        tabs = [None, None]                              # pinned int32 [batch_size, 24] tables, one per slot
+        if aug is not None:
+            from xcp.augment import AUG_COLS
+            tabs = [torch.empty((self.batch_size, AUG_COLS), dtype=torch.int32, pin_memory=True) for _ in range(2)]
         free = [threading.Event(), threading.Event()]   # host buffer may be refilled
         for e in free:
             e.set()
@@ -174,7 +195,11 @@ class PinnedClipReader:
                     if copied[slot] is not None:
                         copied[slot].synchronize()
                     bufs[slot], frames, labels, lengths = self.read_batch(paths, bufs[slot], pin=True)
-                    q.put((slot, frames, labels, lengths))
+                    table = None
+                    if aug is not None:
+                        table = self.augment_table(epoch, i, lengths, frames.shape[2], frames.shape[3]).pack(
+                            tabs[slot][:len(paths)])
+                    q.put((slot, frames, labels, lengths, table))
                 q.put(None)
             except BaseException as exc:   # surfaced on the consumer side
                 q.put(exc)
@@ -188,11 +213,12 @@ class PinnedClipReader:
                     break
                 if isinstance(item, BaseException):
                     raise item
-                slot, frames, labels, lengths = item
+                slot, frames, labels, lengths, table = item
                 with torch.cuda.stream(copy_stream):
                     f = frames.to(self.device, non_blocking=True)
                     ln = lengths.to(self.device, non_blocking=True)
                     lab = labels.to(self.device, non_blocking=True)
+                    tab = None if table is None else table.to(self.device, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(copy_stream)
                 copied[slot] = ev
@@ -201,7 +227,11 @@ class PinnedClipReader:
                 cur.wait_event(ev)
                 for t in (f, ln, lab):
                     t.record_stream(cur)
-                clips = ops.frames_prep(f, ln, self.size, self.dtype, self.channels_last)
+                if tab is None:
+                    clips = ops.frames_prep(f, ln, self.size, self.dtype, self.channels_last)
+                else:
+                    tab.record_stream(cur)
+                    clips, ln = ops.clip_augment(f, ln, tab, aug.size, aug.frames, self.dtype, self.channels_last)
                 yield clips, lab, ln
         finally:
             stop.set()

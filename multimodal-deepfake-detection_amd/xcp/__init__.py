@@ -13,6 +13,7 @@ Layout:
   optim.py      fused clip_grad_norm_ + Adam (a torch.optim.Optimizer)
   attribution.py  input_gradient: d(score)/d(frames) of a clip model (saliency, FGSM / PGD)
   streaming.py    score_in_chunks: a long clip scored chunk by chunk with the LSTM state carried
+  augment.py      ClipAugment / AugmentParams: per-clip crop, flip, colour, erase, frame sampling in one kernel
   heads.py      ArcFace head / CB-focal loss on HIP kernels; metrics.py: ROC / EER / pAUC
 
 Precision of the backbone (activations / GEMM operands; accumulation is fp32, master
@@ -61,6 +62,7 @@ def precision(dt):
 
 from .attribution import input_gradient  # noqa: E402,F401  (d(score)/d(frames) of a clip model)
 from .streaming import score_in_chunks  # noqa: E402,F401  (a long clip, chunk by chunk, LSTM state carried)
+from .augment import AugmentParams, ClipAugment, augment_reference  # noqa: E402,F401  (GPU clip augmentation)
 
 
 def library_path():

@@ -77,6 +77,7 @@ SIGNATURES = {
     "xcp_frames_u8_to_f32": [P, P, P, I, I, I, I, P],
     "xcp_resize_bilinear": [P, P, I, I, I, I, I, P],
     "xcp_frames_prep": [P, P, P, I, I, I, I, I, I, I, I, P],
+    "xcp_clip_augment": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "xcp_opt_sumsq": [P, I, P, F, P, P],
     "xcp_opt_adam": [P, I, P, F, F, F, F, F, F, F, P],
     "xcp_opt_adam_dev": [P, I, P, F, D, D, F, F, P, P],

@@ -141,9 +141,268 @@ void launch_prep(const unsigned char* in, const int* len, void* out, bool nhwc, 
                        sw, total);
 }
 
+// Clip augmentation: the same uint8 clips -> the model's input with a per-clip random crop box
+// resampled to OH x OW, horizontal flip, per-channel affine (contrast / brightness / mean / std),
+// erase rectangle and frame sub-sampling, one read of the clip and one write of the input.
+// tab [B][XCP_AUG_COLS] int32 (device), one row per clip, every frame of the clip uses it:
+//   0 t0, 1 tstride, 2 y0, 3 x0, 4 bh, 5 bw, 6 flip, 7 ey0, 8 ex0, 9 eh, 10 ew, 11 unused,
+//   12-14 a[3], 15-17 b[3], 18-20 fill[3] (fp32 bit patterns), 21-23 unused.
+// Order of operations (the contract augment_reference restates): x / 255; bilinear resample of
+// the box (lin_idx on box-relative indices, products then sums as frames_prep_kernel); flip;
+// v * a[c], then + b[c] (two roundings, no FMA); fill inside the erase rectangle; cast.
+//
+// A 256-thread block makes a 16-row x 128-column tile of one output frame: wave w the rows
+// 4w..4w+3, lane l the columns l and l + 64.  A thread forms its 2 column and 4 row index /
+// weight sets once (the row sets and all row addressing in scalar registers), fetches each
+// source pixel pair (i1 is i0 or i0 + 1: 6 consecutive bytes) with one 8-byte load, all 16 loads
+// ahead of the arithmetic, and computes its two pixels of a row as the halves of packed fp32
+// instructions.  Planar stores are one element per lane along a row; interleaved stores go
+// through three ds_permute so that lane j holds element j, j + 64, j + 128 of the wave's 192
+// contiguous elements.  No LDS.
+constexpr int AUG_COLS = 24, AUG_TR = 16, AUG_TC = 128;
+
+template <bool V> struct AugBool { static constexpr bool value = V; };
+
+struct AugClip {   // one clip's table row, clamped into the valid range
+  int t0, ts, y0, x0, bh, bw, flip, ey_lo, ey_hi, ex_lo, ex_hi, out_len;
+};
+
+XCP_DEV int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+XCP_DEV AugClip aug_clip(const int* __restrict__ r, int len, int Tmax, int Tout, int H, int W, int OH, int OW) {
+  AugClip p;
+  const int L = clampi(len, 0, Tmax);
+  p.t0 = clampi(r[0], 0, Tmax);
+  p.ts = clampi(r[1], 1, Tmax);
+  p.bh = clampi(r[4], 1, H);
+  p.bw = clampi(r[5], 1, W);
+  p.y0 = clampi(r[2], 0, H - p.bh);
+  p.x0 = clampi(r[3], 0, W - p.bw);
+  p.flip = r[6] != 0;
+  const long ey1 = (long)r[7] + r[9], ex1 = (long)r[8] + r[10];   // eh, ew <= 0: empty
+  p.ey_lo = max(r[7], 0);
+  p.ey_hi = (int)(ey1 < (long)OH ? ey1 : (long)OH);
+  p.ex_lo = max(r[8], 0);
+  p.ex_hi = (int)(ex1 < (long)OW ? ex1 : (long)OW);
+  const int n = L > p.t0 ? (L - p.t0 + p.ts - 1) / p.ts : 0;
+  p.out_len = n < Tout ? n : Tout;
+  return p;
+}
+
+// (float)byte / 255.f, correctly rounded, without the division sequence: 1 / 255 as the
+// unevaluated sum of two floats, x * hi + fl(x * lo) in one fma.  Exact for every x in 0..255
+// (all 256 checked against x / 255.f on the host; the GPU tests feed every byte value).
+XCP_DEV f32x2 u8_unit(f32x2 x) {
+  const float hi = 0x1.010102p-8f, lo = -0x1.fdfdfep-33f;
+  const f32x2 l = x * lo;
+  return __builtin_elementwise_fma(x, f32x2{hi, hi}, l);
+}
+
+// channel c of the pixels p0 and p1 (3 bytes each) as floats 0..255
+XCP_DEV f32x2 px2(unsigned p0, unsigned p1, int c) {
+  return f32x2{(float)((p0 >> (8 * c)) & 0xffu), (float)((p1 >> (8 * c)) & 0xffu)};
+}
+
+// The 3 bytes of the source pixel at byte offset off of in (-> p0, byte c = channel c) and of its
+// right neighbour, or of itself again when same (-> p1): lin_idx gives i1 = i0 or i0 + 1, so the
+// two are 6 consecutive bytes and one 8-byte load brings both.  last8 = (bytes of in) - 8 keeps
+// that load inside the buffer: at the buffer's end it starts s <= 2 (a single pixel: s <= 5)
+// bytes early and the wanted bytes are shifted down.  A buffer under 8 bytes is read bytewise.
+// load_px_pair issues the load, split_px_pair (given the same cw, lim, same) takes the bytes
+// apart, so that a thread can issue all its loads before it waits for the first.  The pixel is at
+// byte row + cw of in (row: wave-uniform, cw: per lane); lim = last8 - row, clamped to an int.
+template <bool WIDE>
+XCP_DEV unsigned long long load_px_pair(const unsigned char* __restrict__ in, long row, int cw, int lim, bool same) {
+  unsigned long long u;
+  if (WIDE) {
+    __builtin_memcpy(&u, in + row + min(cw, lim), 8);
+  } else {
+    const unsigned char* s = in + row + cw;
+    const int o1 = same ? 0 : 3;
+    const unsigned p0 = (unsigned)s[0] | (unsigned)s[1] << 8 | (unsigned)s[2] << 16;
+    const unsigned p1 = (unsigned)s[o1] | (unsigned)s[o1 + 1] << 8 | (unsigned)s[o1 + 2] << 16;
+    u = (unsigned long long)p0 | (unsigned long long)p1 << 24;
+  }
+  return u;
+}
+
+template <bool WIDE>
+XCP_DEV void split_px_pair(unsigned long long u, int cw, int lim, bool same, unsigned& p0, unsigned& p1) {
+  if (WIDE) u >>= 8 * (cw - min(cw, lim));
+  p0 = (unsigned)u & 0xffffffu;
+  p1 = same ? p0 : (unsigned)(u >> 24) & 0xffffffu;
+}
+
+// One wave stores the 3 channels v of 64 pixels (lane l: column c0 + l) of output row oh; ok
+// (wave-uniform) = the row and c0 are inside the frame.  Every lane of the wave calls it.
+template <typename T, bool NHWC>
+XCP_DEV void aug_store(T* __restrict__ out, const float* v, int frame, int oh, int c0, int lane, int OH, int OW,
+                       bool ok) {
+  if (NHWC) {
+    // lane l sends channel c to lane (3l + c) mod 64 (3 is invertible mod 64: no collision);
+    // element e = lane + 64k of the wave's 192 is channel e % 3 = (lane + k) % 3 of pixel e / 3
+    float rc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      rc[c] = __int_as_float(__builtin_amdgcn_ds_permute(((3 * lane + c) & 63) * 4, __float_as_int(v[c])));
+    const int nel = ok ? 3 * min(64, OW - c0) : 0, m = lane % 3;
+    T* o = out + (((long)frame * OH + oh) * OW + c0) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int cs = m + k >= 3 ? m + k - 3 : m + k;
+      const float x = cs == 0 ? rc[0] : (cs == 1 ? rc[1] : rc[2]);
+      if (lane + 64 * k < nel) o[lane + 64 * k] = (T)x;
+    }
+  } else if (ok && c0 + lane < OW) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(((long)frame * 3 + c) * OH + oh) * OW + c0 + lane] = (T)v[c];
+  }
+}
+
+template <typename T, bool NHWC>
+__global__ __launch_bounds__(256) void clip_augment_kernel(const unsigned char* __restrict__ in,
+                                                           const int* __restrict__ len, const int* __restrict__ tab,
+                                                           T* __restrict__ out, int* __restrict__ out_len, int Tmax,
+                                                           int Tout, int H, int W, int OH, int OW, int tiles_y,
+                                                           int tiles_x, long last8) {
+#pragma clang fp contract(off)
+  const int per_frame = tiles_y * tiles_x;
+  const int frame = blockIdx.x / per_frame;   // b * Tout + t
+  const int tile = blockIdx.x - frame * per_frame, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int b = frame / Tout, t = frame - b * Tout;
+  const int* row = tab + (long)b * AUG_COLS;
+  const AugClip p = aug_clip(row, len[b], Tmax, Tout, H, W, OH, OW);
+  if (t == 0 && tile == 0 && threadIdx.x == 0) out_len[b] = p.out_len;
+  const bool live = t < p.out_len;   // block-uniform
+  // the wave index and what follows from it (rows, source rows, store bases) in scalar registers
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int oh0 = ty * AUG_TR + wave * 4, ow0 = tx * AUG_TC;
+
+  float av[3], bv[3], fv[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    av[c] = __int_as_float(row[12 + c]);
+    bv[c] = __int_as_float(row[15 + c]);
+    fv[c] = __int_as_float(row[18 + c]);
+  }
+  // per-column sets: byte offsets of the two source columns inside a source row, weights, erase
+  int cw0[2];
+  float clw0[2], clw1[2];
+  bool cer[2], csame[2];
+  const float sh = (float)p.bh / (float)OH, sw = (float)p.bw / (float)OW;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int ow = min(ow0 + j * 64 + lane, OW - 1);   // lanes past the row work on its last column, unstored
+    int w0, w1;
+    lin_idx(p.flip ? OW - 1 - ow : ow, p.bw, sw, w0, w1, clw0[j], clw1[j]);
+    cw0[j] = (p.x0 + w0) * 3;
+    csame[j] = w1 == w0;
+    cer[j] = ow >= p.ex_lo && ow < p.ex_hi;
+  }
+  if (!live) {   // padding frame: zeros, nothing read
+    const float z[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        aug_store<T, NHWC>(out, z, frame, oh0 + i, ow0 + j * 64, lane, OH, OW, oh0 + i < OH && ow0 + j * 64 < OW);
+    return;
+  }
+  const long f = ((long)b * Tmax + p.t0 + t * p.ts) * H * W * 3;   // byte offset of the source frame
+  // Rows past OH recompute row OH - 1 and store nothing.  The thread's 16 loads (4 rows x 2
+  // columns x 2 source rows) are issued before the first is used.
+  auto rows = [&](auto wide) {
+#pragma clang fp contract(off)
+  constexpr bool WIDE = decltype(wide)::value;
+  const f32x2 lw0 = {clw0[0], clw0[1]}, lw1 = {clw1[0], clw1[1]};
+  int lim[4][2];
+  float lh[4][2];
+  unsigned long long u[4][2][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int h[2];
+    lin_idx(min(oh0 + i, OH - 1), p.bh, sh, h[0], h[1], lh[i][0], lh[i][1]);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const long r = f + (long)(p.y0 + __builtin_amdgcn_readfirstlane(h[k])) * W * 3;
+      const long d = last8 - r;
+      lim[i][k] = (int)(d > 0x7fffffffL ? 0x7fffffffL : (d < -0x7fffffffL ? -0x7fffffffL : d));
+#pragma unroll
+      for (int j = 0; j < 2; ++j) u[i][j][k] = load_px_pair<WIDE>(in, r, cw0[j], lim[i][k], csame[j]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int oh = oh0 + i, ohc = min(oh, OH - 1);
+    const float lh0 = lh[i][0], lh1 = lh[i][1];
+    const bool rer = ohc >= p.ey_lo && ohc < p.ey_hi;
+    unsigned q[2][2][2];   // [column set][source row][source column]: a pixel's 3 bytes
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        split_px_pair<WIDE>(u[i][j][k], cw0[j], lim[i][k], csame[j], q[j][k][0], q[j][k][1]);
+    // the thread's two pixels of the row side by side in the halves of f32x2 values: the same
+    // IEEE operations per pixel, in half as many (packed) instructions
+    float v[2][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const f32x2 a = u8_unit(px2(q[0][0][0], q[1][0][0], c)), bb = u8_unit(px2(q[0][0][1], q[1][0][1], c));
+      const f32x2 cc = u8_unit(px2(q[0][1][0], q[1][1][0], c)), d = u8_unit(px2(q[0][1][1], q[1][1][1], c));
+      const f32x2 t0 = a * lw0 + bb * lw1;
+      const f32x2 t1 = cc * lw0 + d * lw1;
+      f32x2 x = t0 * lh0 + t1 * lh1;
+      x = x * av[c];
+      x = x + bv[c];
+      v[0][c] = (rer && cer[0]) ? fv[c] : x.x;
+      v[1][c] = (rer && cer[1]) ? fv[c] : x.y;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      aug_store<T, NHWC>(out, v[j], frame, oh, ow0 + j * 64, lane, OH, OW, oh < OH && ow0 + j * 64 < OW);
+  }
+  };
+  if (last8 >= 0)   // grid-uniform
+    rows(AugBool<true>{});
+  else
+    rows(AugBool<false>{});
+}
+
+template <typename T>
+void launch_augment(const unsigned char* in, const int* len, const int* tab, void* out, int* out_len, bool nhwc,
+                    int Tmax, int Tout, int H, int W, int OH, int OW, int tiles_y, int tiles_x, long last8,
+                    unsigned blocks, hipStream_t st) {
+  if (nhwc)
+    hipLaunchKernelGGL((clip_augment_kernel<T, true>), dim3(blocks), dim3(256), 0, st, in, len, tab, (T*)out, out_len,
+                       Tmax, Tout, H, W, OH, OW, tiles_y, tiles_x, last8);
+  else
+    hipLaunchKernelGGL((clip_augment_kernel<T, false>), dim3(blocks), dim3(256), 0, st, in, len, tab, (T*)out, out_len,
+                       Tmax, Tout, H, W, OH, OW, tiles_y, tiles_x, last8);
+}
+
 }  // namespace
 
 extern "C" {
+
+// Clip augmentation (layout of tab, order of operations: clip_augment_kernel above).  in
+// [B][Tmax][H][W][3] uint8, len [B], tab [B][24] int32 -> out [B][Tout][3][OH][OW] (nhwc 1:
+// [B][Tout][OH][OW][3]) of dtype, out_len [B] int32; all device, stream-ordered, no host read.
+int xcp_clip_augment(const unsigned char* in, const int* len, const int* tab, void* out, int* out_len, int B, int Tmax,
+                     int Tout, int H, int W, int OH, int OW, int dtype, int nhwc, hipStream_t st) {
+  if (B <= 0 || Tout <= 0 || OH <= 0 || OW <= 0) return XCP_OK;
+  if (Tmax <= 0 || H <= 0 || W <= 0 || (dtype != XCP_F32 && dtype != XCP_BF16)) return XCP_EINVAL;
+  const int tiles_y = (OH + AUG_TR - 1) / AUG_TR, tiles_x = (OW + AUG_TC - 1) / AUG_TC;
+  const long blocks = (long)B * Tout * tiles_y * tiles_x;
+  if (blocks > 0x7fffffffL) return XCP_EUNSUPPORTED;
+  const long last8 = (long)B * Tmax * H * W * 3 - 8;   // where the last 8-byte load inside in starts
+  if (dtype == XCP_F32)
+    launch_augment<float>(in, len, tab, out, out_len, nhwc != 0, Tmax, Tout, H, W, OH, OW, tiles_y, tiles_x, last8,
+                          (unsigned)blocks, st);
+  else
+    launch_augment<bf16>(in, len, tab, out, out_len, nhwc != 0, Tmax, Tout, H, W, OH, OW, tiles_y, tiles_x, last8,
+                         (unsigned)blocks, st);
+  return (int)hipGetLastError();
+}
 
 // B clips of up to Tmax uint8 [H][W][3] frames (len: device int32 [B]) -> out at OH x OW:
 // dtype XCP_F32 / XCP_BF16, nhwc 0 = [B][Tmax][3][OH][OW], 1 = [B][Tmax][OH][OW][3]

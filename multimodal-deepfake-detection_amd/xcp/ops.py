@@ -509,6 +509,39 @@ def frames_prep(frames, lengths, size=None, dtype=torch.float32, channels_last=F
     return out.permute(0, 1, 4, 2, 3) if channels_last else out
 
 
+def clip_augment(frames, lengths, params, size, out_frames=None, dtype=torch.float32, channels_last=False):
+    """uint8 [B, T, H, W, 3] frames (device) + int32 [B] lengths + a per-clip table -> (clips
+    [B, Tout, 3, OH, OW] of ``dtype``, out_lengths int32 [B]), one kernel: frame sub-sampling,
+    x / 255, crop box resampled bilinearly to ``size``, flip, per-channel affine, erase, cast
+    (xcp.augment.augment_reference restates the order of operations; include/xcp.h the table).
+    params: an ``xcp.augment.AugmentParams`` (validated here, then packed and copied to the
+    device) or its packed device form ``params.to(device)``, int32 [B, 24], which the kernel
+    clamps instead.  out_frames: Tout (default T).  channels_last: as ``frames_prep``."""
+    from .augment import AUG_COLS, AugmentParams
+    check_gpu(frames, lengths)
+    B, T, H, W, C = frames.shape
+    if C != 3 or frames.dtype != torch.uint8 or lengths.dtype != torch.int32 or lengths.numel() != B \
+            or dtype not in DT:
+        raise ValueError("clip_augment: expects uint8 [B,T,H,W,3], int32 [B], fp32 / bf16 output")
+    OH, OW = size
+    Tout = T if out_frames is None else int(out_frames)
+    if OH < 1 or OW < 1 or Tout < 1:
+        raise ValueError("clip_augment: size and out_frames must be positive")
+    if isinstance(params, AugmentParams):
+        params.validate(B, H, W)
+        params = params.to(frames.device)
+    check_gpu(params)
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, AUG_COLS) or not params.is_contiguous():
+        raise ValueError(f"clip_augment: the device table is a contiguous int32 [B, {AUG_COLS}] tensor")
+    frames, lengths = frames.contiguous(), lengths.contiguous()
+    shape = (B, Tout, OH, OW, 3) if channels_last else (B, Tout, 3, OH, OW)
+    out = torch.empty(shape, device=frames.device, dtype=dtype)
+    out_len = torch.empty(B, device=frames.device, dtype=torch.int32)
+    _lib.call("xcp_clip_augment", _p(frames), _p(lengths), _p(params), _p(out), _p(out_len), B, T, Tout, H, W, OH, OW,
+              DT[dtype], 1 if channels_last else 0, stream())
+    return (out.permute(0, 1, 4, 2, 3) if channels_last else out), out_len
+
+
 def resize_bilinear(x, size):
     """F.interpolate(x, size, mode="bilinear", align_corners=False) for fp32 NCHW x on the GPU
     (the XceptionLSTMA front end, XceptionLSTMA.py:46)."""
