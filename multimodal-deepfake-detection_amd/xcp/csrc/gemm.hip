@@ -579,7 +579,7 @@ __global__ __launch_bounds__(512) void gemm_nt256k64_kernel(NTArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
-// Persistent 256x256 NT kernel: the main loop of gemm_nt256k64_kernel, one workgroup per CU
+// Persistent 256x256 NT kernel (gemm_nt256p_kernel): the main loop of gemm_nt256k64_kernel, one workgroup per CU
 // walking its tiles (round r: tile r * grid + its XCD-remapped slot, so each round keeps the
 // A-row sharing of the one-shot kernel).  Per tile the one-shot kernel pays a fixed cost of
 // ~8-15 us at K = 736 (tools/gemm_probe.py: launch boundary, the first K-tile's fill latency and
@@ -591,34 +591,15 @@ __global__ __launch_bounds__(512) void gemm_nt256k64_kernel(NTArgs a) {
 // a K-tile-1 load (phase Q3) retires them.  Every epilogue store is a buffer store whose masked
 // lanes get an out-of-range offset, so each wave issues exactly S store instructions and the
 // counts are exact (a skipped, fully masked store would make a count one short: a race).
-XCP_DEV void vm_wait(int n) {   // s_waitcnt vmcnt(n), n in [0, 63] (folds when n is constant)
-  switch (n < 0 ? 0 : n > 63 ? 63 : n) {
-#define XCP_VMW(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    XCP_VMW(0) XCP_VMW(1) XCP_VMW(2) XCP_VMW(3) XCP_VMW(4) XCP_VMW(5) XCP_VMW(6) XCP_VMW(7)
-    XCP_VMW(8) XCP_VMW(9) XCP_VMW(10) XCP_VMW(11) XCP_VMW(12) XCP_VMW(13) XCP_VMW(14) XCP_VMW(15)
-    XCP_VMW(16) XCP_VMW(17) XCP_VMW(18) XCP_VMW(19) XCP_VMW(20) XCP_VMW(21) XCP_VMW(22) XCP_VMW(23)
-    XCP_VMW(24) XCP_VMW(25) XCP_VMW(26) XCP_VMW(27) XCP_VMW(28) XCP_VMW(29) XCP_VMW(30) XCP_VMW(31)
-    XCP_VMW(32) XCP_VMW(33) XCP_VMW(34) XCP_VMW(35) XCP_VMW(36) XCP_VMW(37) XCP_VMW(38) XCP_VMW(39)
-    XCP_VMW(40) XCP_VMW(41) XCP_VMW(42) XCP_VMW(43) XCP_VMW(44) XCP_VMW(45) XCP_VMW(46) XCP_VMW(47)
-    XCP_VMW(48) XCP_VMW(49) XCP_VMW(50) XCP_VMW(51) XCP_VMW(52) XCP_VMW(53) XCP_VMW(54) XCP_VMW(55)
-    XCP_VMW(56) XCP_VMW(57) XCP_VMW(58) XCP_VMW(59) XCP_VMW(60) XCP_VMW(61) XCP_VMW(62) XCP_VMW(63)
-#undef XCP_VMW
-  }
-}
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
 // epilogue256_regs with buffer stores (always issued; OOB offset for masked lanes):
 // 16 C stores per lane, + 1 statistics store when STATS
-// (FENCE: no instruction moves across a row block's end -- for accumulators in AGPRs, whose reads the
-// scheduler otherwise hoists all at once into VGPRs.  SKIP: a store whose every lane is out of range is not
-// issued (wave-uniform test), and the count of store instructions issued is returned: a store dropped whole by
-// the range check was seen to retire its vmcnt ahead of older loads, which a counted wait cannot allow for)
-template <bool STATS, typename Get, bool FENCE = false, bool SKIP = false>
-XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC, __amdgpu_buffer_rsrc_t rS, int m0,
-                            int n0, int wr, int wc, int fr, int fg) {
-  int issued = 0;
+template <bool STATS>
+XCP_DEV void epilogue256_buf(f32x4 (&acc)[8][4], const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
+                             __amdgpu_buffer_rsrc_t rS, int m0, int n0, int wr, int wc, int fr, int fg) {
   const int bm = m0 / 256, stat_rows = (a.M + 127) / 128;
   const int mrow = m0 + wr * 128 + fr;
   const int ncol = n0 + wc * 64;
@@ -632,7 +613,7 @@ XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
     const bool mok = m < a.M;
     uint2 pc[4];
     static_for<0, 4>([&](auto j) {
-      pc[j] = make_uint2(pk_bf16(acc(i, j, 0), acc(i, j, 1)), pk_bf16(acc(i, j, 2), acc(i, j, 3)));
+      pc[j] = make_uint2(pk_bf16(acc[i][j][0], acc[i][j][1]), pk_bf16(acc[i][j][2], acc[i][j][3]));
       const bf16x4 q = __builtin_bit_cast(bf16x4, pc[j]);
       if constexpr (STATS) {   // (branch-free: rows past M add zero)
 #pragma unroll
@@ -660,21 +641,8 @@ XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
     // sc1 write-through measured slower: profiles/r06_nt_cstore_ab.txt)
     // (A/B: tools/exp/gemm_cnt.hip / gemm_csc1.hip were this file with the policy argument 2 / 16 instead of 0;
     // a runtime-selected policy costs the persistent kernel 18 more spilled SGPRs, so it is fixed here)
-    if constexpr (SKIP) {
-      const bool rows = m0 + wr * 128 + i * 16 < a.M;   // (wave-uniform: some row of the block in range)
-      if (rows && ncol < a.N) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st0), rC, (int)o0, 0, 2);
-        ++issued;
-      }
-      if (rows && ncol + 32 < a.N) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st1), rC, (int)o1, 0, 2);
-        ++issued;
-      }
-    } else {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st0), rC, (int)o0, 0, 2);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st1), rC, (int)o1, 0, 2);
-    }
-    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st0), rC, (int)o0, 0, 2);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st1), rC, (int)o1, 0, 2);
   });
   if constexpr (STATS) {
     float u[16], v8[8], v4[4], v2[2];
@@ -691,18 +659,8 @@ XCP_DEV int epilogue256_get(Get acc, const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
     const int srow = bm * 2 + wr;
     const unsigned so = (srow < stat_rows && col < a.N)
                             ? (unsigned)((((long)srow * 2 + (fr >> 3)) * a.N + col) * 4) : BUF_OOB;
-    if (!SKIP || (bm * 2 + wr < stat_rows && ncol < a.N)) {
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, make_float2(v2[0], v2[1])), rS, (int)so, 0, 0);
-      ++issued;
-    }
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, make_float2(v2[0], v2[1])), rS, (int)so, 0, 0);
   }
-  return issued;
-}
-
-template <bool STATS>
-XCP_DEV void epilogue256_buf(f32x4 (&acc)[8][4], const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
-                             __amdgpu_buffer_rsrc_t rS, int m0, int n0, int wr, int wc, int fr, int fg) {
-  epilogue256_get<STATS>([&](int i, int j, int r) { return acc[i][j][r]; }, a, rC, rS, m0, n0, wr, wc, fr, fg);
 }
 
 // Tile counters of the persistent NT kernel, one per (device, stream) slot: a workgroup takes its first
@@ -896,323 +854,6 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
-// Persistent 256x256 NT kernel at ONE wave per SIMD (gemm_nt4w_kernel; opt-in XCP_NT_4W=1 while measured).
-//
-// The 8-wave kernels above split a 256x256 tile into 128x64 wave tiles (two waves per SIMD) and pay
-// 8 s_barrier per 64-deep K-tile around 16-MFMA phases (profiles/r04_nt_probe.txt: that skeleton is
-// 0.45 us per K-tile over 0.86 us of MFMA issue).  Here 4 waves each own a 128x128 quarter (64
-// accumulators, 256 registers; 512 per wave at one wave per SIMD):
-//   * K advances in 32-deep steps through a 4-slot LDS ring (32 KB per step: A and B 256 rows x 64 B);
-//     steps g+1 .. g+3 are in flight while step g computes, and step g+4 is issued into g's slot;
-//   * ONE barrier per step: after it every wave's pieces of step g+1 have landed (each wave waits for
-//     its own by a counted vmcnt) and every wave has its step-g fragments in registers (lgkmcnt(0)
-//     before the barrier), so g's slot is refilled and g+1's fragments are read while g's 64 MFMAs
-//     run (fragments double-buffered in registers);
-//   * the fill is one continuous stream over the workgroup's tiles: a tile's last steps issue the next
-//     tile's first ones, so there is no per-tile prologue; the epilogue's stores (32 + 1 per wave) then
-//     stay in flight through the next tile's first three steps.  Past the walk's end the stream
-//     re-issues its last tile's first step (real loads), so every step counts the same instructions.
-// Operand images: rows of 64 B, 16-B chunk c of row r at chunk c ^ f((r >> 2) & 3), f = (0, 2, 3, 1):
-// every lane group of a ds_read_b128 fragment read (rows fr, chunks fg) then covers 16 distinct bank
-// quads.  LDS-DMA writes 16 B per lane at consecutive addresses, so the swizzle is applied to the
-// source: lane l of a piece fetches row (l >> 2), logical chunk (l & 3) ^ f(l >> 4).
-// C and the BN statistics: the 256p kernel's operand order, K order, epilogue packing and statistics
-// reduction tree, so both are bitwise equal to it.
-constexpr int W4_OP = 256 * 64;     // one operand of one 32-deep K-step (16 KB)
-constexpr int W4_SLOT = 2 * W4_OP;  // A + B
-constexpr int W4_NS = 4;
-
-XCP_DEV int w4_f(int q) { return (0x1320 >> (q * 4)) & 3; }
-// the MFMA by inline asm with the accumulator pinned to AGPRs and the operands to VGPRs: with 256 accumulator
-// registers and 128 fragment registers the builtin's register-class choice shuttled accumulators between the
-// two files (v_accvgpr_write / read around every MFMA, and spills).  hipcc pads no hazard for an asm MFMA:
-// the accumulators are zeroed >= 4 wait states before the first one reads them and read back only after an
-// s_nop pad (w4_pad), and the fragments come from ds_read (no VALU-write -> MFMA-read hazard)
-XCP_DEV void w4_mfma(f32x4& c, const bf16x8& a, const bf16x8& b) {
-  asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-XCP_DEV void w4_pad() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory"); }
-XCP_DEV int w4_swz(int r, int c) { return r * 64 + ((c ^ w4_f((r >> 2) & 3)) << 4); }
-
-template <bool STATS, bool W4_ILV>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_nt4w_kernel(NTArgs a) {
-  constexpr bool w4_ilv = W4_ILV;
-  // the ring, then 16 KB of zeros: the fragments of a padding step are read from there
-  __shared__ __attribute__((aligned(16))) char smem[W4_NS * W4_SLOT + W4_OP];
-  const int gridN = (a.N + 255) / 256, gridM = (a.M + 255) / 256;
-  const int tiles = gridM * gridN, nwg = gridDim.x;
-  const int slot = xcd_remap(blockIdx.x, nwg);
-  if (slot >= tiles) return;
-  for (int i = threadIdx.x; i < W4_OP / 16; i += 256)
-    reinterpret_cast<uint4*>(smem + W4_NS * W4_SLOT)[i] = make_uint4(0u, 0u, 0u, 0u);
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 1, wc = w & 1;
-  const int fr = lane & 15, fg = lane >> 4;
-  // 32-deep steps: nkr of them, walked as an even number nk (an odd count gets one more step that loads step 0's
-  // data again -- no load past K is ever issued whole -- and multiplies fragments read from the zero block:
-  // the accumulators start at +0, so adding the +-0 products leaves every bit as it was)
-  const int nkr = (a.K + 31) / 32, nk = (nkr + 1) & ~1;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.A), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.B), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(a.C, (short)0, BUF_RECORDS, BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(STATS ? (void*)a.stats : a.C, (short)0,
-                                                                       BUF_RECORDS, BUF_DWORD3);
-  // ---- the fill stream: wave w loads rows w*64 .. w*64+63 of both operands, 4 pieces of 16 rows each
-  const int lrow = w * 64 + (lane >> 2);           // + 16 i
-  const int lc = (lane & 3) ^ w4_f(lane >> 4);    // logical chunk of this lane ((row >> 2) & 3 == lane >> 4)
-  unsigned va[4], vb[4];                          // this lane's chunk offsets in the fill tile (BUF_OOB: past M / N)
-  int dt = slot, dks = 0, nfill = 0;              // fill pointer: tile, step; steps issued
-  auto set_fill = [&](int t) __attribute__((always_inline)) {
-    const int m0 = (t / gridN) * 256, n0 = (t % gridN) * 256;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ra = m0 + lrow + 16 * i, rb = n0 + lrow + 16 * i;
-      va[i] = ra < a.M ? (unsigned)(((long)ra * a.lda + lc * 8) * 2) : BUF_OOB;
-      vb[i] = rb < a.N ? (unsigned)(((long)rb * a.ldb + lc * 8) * 2) : BUF_OOB;
-    }
-  };
-  auto piece = [&](int q, int ks) __attribute__((always_inline)) {   // piece q (A 0..3, B 4..7) of step ks into slot nfill % 4
-    ks = ks < nkr ? ks : 0;
-    char* d = smem + (nfill & 3) * W4_SLOT + (q < 4 ? 0 : W4_OP) + (w * 64 + 16 * (q & 3)) * 64;
-    const unsigned v = q < 4 ? va[q & 3] : vb[q & 3];
-    const unsigned o = (ks * 32 + lc * 8 < a.K && v != BUF_OOB) ? v + ks * 64 : BUF_OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(q < 4 ? rA : rB, (__attribute__((address_space(3))) void*)d, 16, o, 0, 0, 0);
-  };
-  auto fill_next = [&]() __attribute__((always_inline)) {   // (past the walk: the last tile's step 0 again)
-    ++nfill;
-    if (dt < tiles && ++dks == nk) {
-      dks = 0;
-      if (dt + nwg < tiles) {
-        dt += nwg;
-        set_fill(dt);
-      } else {
-        dt = tiles;
-      }
-    }
-  };
-  set_fill(dt);
-#pragma unroll 1
-  for (int s = 0; s < W4_NS; ++s) {
-    const int ks = dks;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) piece(q, ks);
-    fill_next();
-  }
-
-  f32x4 acc[8][8];
-  bf16x8 fa[2][8], fb[2][8];
-  auto read_frag_at = [&](auto P, int q, int sl) __attribute__((always_inline)) {   // fragments q of the step in slot sl % 4
-    const char* sa = smem + (sl & 3) * W4_SLOT;
-    fa[P][q] = *reinterpret_cast<const bf16x8*>(sa + w4_swz(wr * 128 + q * 16 + fr, fg));
-    fb[P][q] = *reinterpret_cast<const bf16x8*>(sa + W4_OP + w4_swz(wc * 128 + q * 16 + fr, fg));
-  };
-  auto read_frag = [&](auto P, int q, bool zero) __attribute__((always_inline)) {   // fragments q of the step in slot (nfill + 1) % 4
-    const char* sa = zero ? smem + W4_NS * W4_SLOT : smem + ((nfill + 1) & 3) * W4_SLOT;
-    const char* sb = zero ? smem + W4_NS * W4_SLOT : sa + W4_OP;
-    fa[P][q] = *reinterpret_cast<const bf16x8*>(sa + w4_swz(wr * 128 + q * 16 + fr, fg));
-    fb[P][q] = *reinterpret_cast<const bf16x8*>(sb + w4_swz(wc * 128 + q * 16 + fr, fg));
-  };
-  // step 0's fragments
-  vm_wait(24);
-  __builtin_amdgcn_s_barrier();
-  {
-    const char* sa = smem;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      fa[0][q] = *reinterpret_cast<const bf16x8*>(sa + w4_swz(wr * 128 + q * 16 + fr, fg));
-      fb[0][q] = *reinterpret_cast<const bf16x8*>(sa + W4_OP + w4_swz(wc * 128 + q * 16 + fr, fg));
-    }
-  }
-  // one step: fill step g+4 into g's slot, read g+1's fragments, g's 64 MFMAs (C: g's register set)
-  auto step = [&](auto C, bool zn) __attribute__((always_inline)) {   // (zn: the next step is a padding step)
-    constexpr int X = 1 - decltype(C)::value;
-    const int ks = dks;
-    static_for<0, 8>([&](auto q) __attribute__((always_inline)) {
-      piece(q, ks);
-      read_frag(IC<X>{}, q, zn);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w4_mfma(acc[q][j], fb[C][j], fa[C][q]);
-      if (w4_ilv) __builtin_amdgcn_sched_barrier(0);   // (W4_ILV: each group's piece and reads beside its MFMAs)
-    });
-    fill_next();
-  };
-  int st = 0;   // store instructions of the last epilogue (younger than the fills of a tile's first three steps)
-  // step ks of a tile: step g+1 landed (younger: steps g+2, g+3 and, for a tile's first three steps, the last
-  // epilogue's stores); this wave's step-g fragments are in registers (every wave's, after the barrier)
-  auto sync = [&](int ks) __attribute__((always_inline)) {
-    if (ks < 3) vm_wait(16 + st);
-    else vm_wait(16);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  // one tile: an even number of steps (K padded with zero chunks to a multiple of 64: the accumulators start at
-  // +0 and a zero product adds exactly nothing, so C is unchanged) alternating fragment sets 0 and 1; its last
-  // step reads the next tile's first fragments (already landed: the stream is continuous) into set 0
-  auto tile_body = [&](int t) __attribute__((always_inline)) {
-    const int m0 = (t / gridN) * 256, n0 = (t % gridN) * 256;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    w4_pad();
-#pragma unroll 1
-    for (int ks = 0; ks < nk; ks += 2) {
-      sync(ks);
-      step(IC<0>{}, ks + 1 >= nkr);
-      __builtin_amdgcn_sched_barrier(0);
-      sync(ks + 1);
-      step(IC<1>{}, false);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    w4_pad();   // (the last MFMAs' results, before the epilogue reads the accumulators)
-    // ---- epilogue: the 256p kernel's, once per 64-column half of the wave's quarter (16-B nt stores of 8
-    // columns; BN partial sums per 128 rows, the same reduction tree, so C and the sums are bitwise its)
-    int ns = 0;
-    static_for<0, 2>([&](auto h) __attribute__((always_inline)) {
-      auto get = [&](int i, int j, int r) __attribute__((always_inline)) {   // one accumulator, AGPR -> VGPR
-        float v;
-        asm("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[i][4 * h + j][r]));
-        return v;
-      };
-      ns += epilogue256_get<STATS, decltype(get), true, true>(get, a, rC, rS, m0, n0, wr, 2 * wc + h, fr, fg);
-    });
-    st = ns;
-  };
-#pragma unroll 1
-  for (int t = slot; t < tiles; t += nwg) tile_body(t);
-  vm_wait(0);
-}
-
-// ---------------------------------------------------------------------------------
-// Persistent 256x256 NT kernel, 8 waves (two per SIMD, 128x64 each as the 256p kernel) on the 4W kernel's ring
-// (gemm_nt8w_kernel; opt-in XCP_NT_8W=1 while measured): 32-deep steps through 4 LDS slots, ONE barrier per
-// step, the fill one stream over the workgroup's tiles (each wave 4 LDS-DMA pieces per step).  No phase
-// structure: the two waves of a SIMD interleave by themselves, one's fill issue and fragment reads beside the
-// other's MFMAs.  A fragments roll (row block q's next-step fragment is read right after its last MFMA), B
-// fragments are double-buffered; padding step, store counting and epilogue as gemm_nt4w_kernel.
-template <bool STATS>
-__global__ __launch_bounds__(512) void gemm_nt8w_kernel(NTArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[W4_NS * W4_SLOT + W4_OP];
-  const int gridN = (a.N + 255) / 256, gridM = (a.M + 255) / 256;
-  const int tiles = gridM * gridN, nwg = gridDim.x;
-  const int slot = xcd_remap(blockIdx.x, nwg);
-  if (slot >= tiles) return;
-  for (int i = threadIdx.x; i < W4_OP / 16; i += 512)
-    reinterpret_cast<uint4*>(smem + W4_NS * W4_SLOT)[i] = make_uint4(0u, 0u, 0u, 0u);
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 2, wc = w & 3;
-  const int fr = lane & 15, fg = lane >> 4;
-  const int nkr = (a.K + 31) / 32, nk = (nkr + 1) & ~1;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.A), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.B), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(a.C, (short)0, BUF_RECORDS, BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(STATS ? (void*)a.stats : a.C, (short)0,
-                                                                       BUF_RECORDS, BUF_DWORD3);
-  // ---- the fill stream: wave w loads rows w*32 .. w*32+31 of both operands, 2 pieces of 16 rows each
-  const int lrow = w * 32 + (lane >> 2);
-  const int lc = (lane & 3) ^ w4_f(lane >> 4);
-  unsigned va[2], vb[2];
-  int dt = slot, dks = 0, nfill = 0;
-  auto set_fill = [&](int t) __attribute__((always_inline)) {
-    const int m0 = (t / gridN) * 256, n0 = (t % gridN) * 256;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ra = m0 + lrow + 16 * i, rb = n0 + lrow + 16 * i;
-      va[i] = ra < a.M ? (unsigned)(((long)ra * a.lda + lc * 8) * 2) : BUF_OOB;
-      vb[i] = rb < a.N ? (unsigned)(((long)rb * a.ldb + lc * 8) * 2) : BUF_OOB;
-    }
-  };
-  auto piece = [&](int q, int ks) __attribute__((always_inline)) {   // piece q (A 0..1, B 2..3) into slot nfill % 4
-    ks = ks < nkr ? ks : 0;
-    char* d = smem + (nfill & 3) * W4_SLOT + (q < 2 ? 0 : W4_OP) + (w * 32 + 16 * (q & 1)) * 64;
-    const unsigned v = q < 2 ? va[q & 1] : vb[q & 1];
-    const unsigned o = (ks * 32 + lc * 8 < a.K && v != BUF_OOB) ? v + ks * 64 : BUF_OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(q < 2 ? rA : rB, (__attribute__((address_space(3))) void*)d, 16, o, 0, 0, 0);
-  };
-  auto fill_next = [&]() __attribute__((always_inline)) {
-    ++nfill;
-    if (dt < tiles && ++dks == nk) {
-      dks = 0;
-      if (dt + nwg < tiles) {
-        dt += nwg;
-        set_fill(dt);
-      } else {
-        dt = tiles;
-      }
-    }
-  };
-  set_fill(dt);
-#pragma unroll 1
-  for (int s = 0; s < W4_NS; ++s) {
-    const int ks = dks;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) piece(q, ks);
-    fill_next();
-  }
-  f32x4 acc[8][4];
-  bf16x8 fa[8], fb[2][4];
-  auto abase = [&](bool zero) __attribute__((always_inline)) {   // the step in slot (nfill + 1) % 4, or the zero block
-    return zero ? smem + W4_NS * W4_SLOT : smem + ((nfill + 1) & 3) * W4_SLOT;
-  };
-  vm_wait(12);
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int q = 0; q < 8; ++q) fa[q] = *reinterpret_cast<const bf16x8*>(smem + w4_swz(wr * 128 + q * 16 + fr, fg));
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    fb[0][j] = *reinterpret_cast<const bf16x8*>(smem + W4_OP + w4_swz(wc * 64 + j * 16 + fr, fg));
-  auto step = [&](auto C, bool zn) __attribute__((always_inline)) {   // (zn: the next step is a padding step)
-    constexpr int X = 1 - decltype(C)::value;
-    const int ks = dks;
-    const char* sa = abase(zn);
-    const char* sb = zn ? sa : sa + W4_OP;
-    static_for<0, 8>([&](auto q) __attribute__((always_inline)) {
-      if constexpr (q < 4) piece(q, ks);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[q][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[C][j], fa[q], acc[q][j], 0, 0, 0);
-      fa[q] = *reinterpret_cast<const bf16x8*>(sa + w4_swz(wr * 128 + q * 16 + fr, fg));
-      if constexpr (q < 4) fb[X][q] = *reinterpret_cast<const bf16x8*>(sb + w4_swz(wc * 64 + q * 16 + fr, fg));
-    });
-    fill_next();
-  };
-  int st = 0;   // store instructions of the last epilogue (younger than the fills of a tile's first three steps)
-  auto sync = [&](int ks) __attribute__((always_inline)) {
-    if (ks < 3) vm_wait(8 + st);
-    else vm_wait(8);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#pragma unroll 1
-  for (int t = slot; t < tiles; t += nwg) {
-    const int m0 = (t / gridN) * 256, n0 = (t % gridN) * 256;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int ks = 0; ks < nk; ks += 2) {
-      sync(ks);
-      step(IC<0>{}, ks + 1 >= nkr);
-      __builtin_amdgcn_sched_barrier(0);
-      sync(ks + 1);
-      step(IC<1>{}, false);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    auto get = [&](int i, int j, int r) __attribute__((always_inline)) { return acc[i][j][r]; };
-    st = epilogue256_get<STATS, decltype(get), false, true>(get, a, rC, rS, m0, n0, wr, wc, fr, fg);
-  }
-  vm_wait(0);
-}
-
-// ---------------------------------------------------------------------------------
 // Persistent 256x256 NT kernel, two MFMA phases per 64-deep K-tile and the fill issued ~1.5
 // K-tiles ahead (gemm_nt256q_kernel, the default; XCP_NT_LOOP=4 keeps gemm_nt256p_kernel).
 //
@@ -1284,7 +925,7 @@ XCP_DEV void epilogue256_half(f32x4 (&acc)[8][4], const NTArgs& a, __amdgpu_buff
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st0), rC, (int)o0, 0, 0);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st1), rC, (int)o1, 0, 0);
   });
-  if constexpr (STATS) {   // this half's column sums, reduced over the wave as epilogue256_get does
+  if constexpr (STATS) {   // this half's column sums, reduced over the wave as epilogue256_buf does
     float u[16], v8[8], v4[4];
     const bool b3 = fr & 8, b2 = fr & 4, b1 = fr & 2, b0 = fr & 1;
 #pragma unroll
@@ -2027,25 +1668,24 @@ namespace {
 // one 160 KB-LDS workgroup on every CU left those no room, half the CUs (and half the split-K
 // slabs) measured 1.0-1.8 % faster per step for targets 64-192 (profiles/r02_tn_target_sweep.txt).
 constexpr int TN_TARGET_WGS_DEFAULT = 128;
+
+// The A/B switches: first character of environment variable `name`, 0 when it is unset or empty.  A predicate
+// marked "per call" reads its variable at every call (the tests flip those between calls); the ones that keep
+// a `static const` read theirs once per process.
+char env0(const char* name) {
+  const char* e = getenv(name);
+  return e ? e[0] : 0;
+}
 bool tn_xcd_splits() {   // XCP_TN_XCD_SPLITS=1 (A/B; measured -0.3 % in the step, off)
-  static const bool v = [] {
-    const char* e = getenv("XCP_TN_XCD_SPLITS");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env0("XCP_TN_XCD_SPLITS") == '1';
   return v;
 }
 // The weight-gradient kernel with one 32-MFMA phase per step and the fill 4 steps ahead (gemm_tn256q_kernel):
 // 9-13 % faster alone at every step shape, the partial slabs bitwise equal (profiles/r06_tn_loop_ab.txt).
 // XCP_TN_LOOP=1: gemm_tn256_kernel's two 16-MFMA phases (read per call; A/B)
-bool tn_loop2() {
-  const char* e = getenv("XCP_TN_LOOP");
-  return !(e && e[0] == '1');
-}
+bool tn_loop2() { return env0("XCP_TN_LOOP") != '1'; }
 // XCP_TN_XCD_ALIGN=1: whole splits per XCD for outputs of at most 32 tiles (read per call; A/B)
-bool tn_xcd_align() {
-  const char* e = getenv("XCP_TN_XCD_ALIGN");
-  return e && e[0] == '1';
-}
+bool tn_xcd_align() { return env0("XCP_TN_XCD_ALIGN") == '1'; }
 int tn_target_wgs() {   // XCP_TN_TARGET_WGS=<n> overrides the default (A/B of the side-stream share)
   static const int v = [] {
     const char* e = getenv("XCP_TN_TARGET_WGS");
@@ -2080,18 +1720,12 @@ int nt_big_min_k() {   // XCP_NT_BIG_MINK=<k>: smallest K the automatic choice g
 // (5,531,904 x 128 x 64 / 128: 459 / 567 us there against 552 / 680 on the 256x256 one).
 // XCP_NT_BIG_N256=0 restores the K >= 384 rule alone (A/B).
 bool nt_big_n256() {
-  static const bool v = [] {
-    const char* e = getenv("XCP_NT_BIG_N256");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env0("XCP_NT_BIG_N256") != '0';
   return v;
 }
 
 // XCP_NT_SPARSE=0: no sparse last round (every row on the persistent kernel; read per call; A/B)
-bool nt_sparse() {
-  const char* e = getenv("XCP_NT_SPARSE");
-  return !(e && e[0] == '0');
-}
+bool nt_sparse() { return env0("XCP_NT_SPARSE") != '0'; }
 
 bool nt_big(int dtype, int gmode, int M, int N, int K, int tile) {
   if (dtype != XCP_BF16 || gmode != 0 || tile == 1) return false;
@@ -2105,44 +1739,20 @@ bool tn_big(int dtype, int gmode, int N, int K, int tile) {
   if (dtype != XCP_BF16 || gmode != 0 || tile == 1) return false;
   return tile == 2 || (N >= 256 && K >= 256);
 }
-}  // namespace
 
-// XCP_NT_LOOP=4: the persistent NT kernel with four MFMA phases per K-tile (gemm_nt256p_kernel) instead of
-// two (gemm_nt256q_kernel; A/B, read per call)
-bool nt_loop2() {
-  const char* e = getenv("XCP_NT_LOOP");
-  return e && e[0] == '2';
-}
-bool nt_8w() {   // XCP_NT_8W=1: gemm_nt8w_kernel for the persistent calls from K = 128 (read per call; A/B)
-  const char* e = getenv("XCP_NT_8W");
-  return e && e[0] == '1';
-}
-bool nt_4w() {   // XCP_NT_4W=1 / 2: gemm_nt4w_kernel (one wave per SIMD) for the persistent calls from K = 128 (read per call; A/B)
-  const char* e = getenv("XCP_NT_4W");
-  return e && (e[0] == '1' || e[0] == '2');
-}
-bool nt_4w_ilv() {   // XCP_NT_4W=2: its steps fenced per 8-MFMA group
-  const char* e = getenv("XCP_NT_4W");
-  return e && e[0] == '2';
-}
+// XCP_NT_LOOP=2: the persistent NT kernel with two MFMA phases per K-tile (gemm_nt256q_kernel) instead of
+// the four of gemm_nt256p_kernel (A/B, read per call)
+bool nt_loop2() { return env0("XCP_NT_LOOP") == '2'; }
 // The 256p kernel's last K-tile multiplies only its first 32-deep half when the rest of it is past K (the
 // 728-channel flow at its 736 pitch: K = 728 / 736, 24 / 32 of the last 64): 32 of the tile's 768 MFMAs
 // per wave skipped, C and the statistics bitwise equal (the skipped products are +0).  XCP_NT_KHALF=0:
 // every K-tile whole (read per call; A/B)
-bool nt_khalf() {
-  const char* e = getenv("XCP_NT_KHALF");
-  return !(e && e[0] == '0');
-}
-
+bool nt_khalf() { return env0("XCP_NT_KHALF") != '0'; }
 // XCP_NT_DYNQ=0: the persistent NT kernel walks its static tile list (A/B; read per call)
-bool nt_dynq() {
-  const char* e = getenv("XCP_NT_DYNQ");
-  return !(e && e[0] == '0');
-}
-bool nt_sparse_dgrad() {   // XCP_NT_SPARSE_DGRAD=1 (A/B; read per call)
-  const char* e = getenv("XCP_NT_SPARSE_DGRAD");
-  return e && e[0] == '1';
-}
+bool nt_dynq() { return env0("XCP_NT_DYNQ") != '0'; }
+// XCP_NT_SPARSE_DGRAD=1 (A/B; read per call)
+bool nt_sparse_dgrad() { return env0("XCP_NT_SPARSE_DGRAD") == '1'; }
+
 // A tile-queue counter is keyed by the (device, stream) of the launch, and each launch relies on being
 // its counter's only user between its first fetch and its last (which resets it).  Launches on one
 // stream are ordered, so eager use is safe.  A graph node would keep the capture stream's counter
@@ -2166,6 +1776,7 @@ int nt_tq_slot(hipStream_t st) {
   slots.emplace_back(dev, st);
   return (int)slots.size();
 }
+}  // namespace
 
 extern "C" {
 
@@ -2212,21 +1823,6 @@ int xcp_gemm_nt(int dtype, const void* A, long lda, const void* B, long ldb, voi
           hipLaunchKernelGGL(gemm_nt256q_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
         else
           hipLaunchKernelGGL(gemm_nt256q_kernel<false>, dim3(grid), dim3(512), 0, stream, big);
-      } else if (nt_8w() && K >= 128) {
-        if (stats)
-          hipLaunchKernelGGL(gemm_nt8w_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
-        else
-          hipLaunchKernelGGL(gemm_nt8w_kernel<false>, dim3(grid), dim3(512), 0, stream, big);
-      } else if (nt_4w() && K >= 128) {
-        const bool ilv = nt_4w_ilv();
-        if (stats && ilv)
-          hipLaunchKernelGGL((gemm_nt4w_kernel<true, true>), dim3(grid), dim3(256), 0, stream, big);
-        else if (stats)
-          hipLaunchKernelGGL((gemm_nt4w_kernel<true, false>), dim3(grid), dim3(256), 0, stream, big);
-        else if (ilv)
-          hipLaunchKernelGGL((gemm_nt4w_kernel<false, true>), dim3(grid), dim3(256), 0, stream, big);
-        else
-          hipLaunchKernelGGL((gemm_nt4w_kernel<false, false>), dim3(grid), dim3(256), 0, stream, big);
       } else if (stats)
         hipLaunchKernelGGL(gemm_nt256p_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
       else

@@ -1366,26 +1366,21 @@ def test_gemm_tn_loops_bitwise(ops, gpu, monkeypatch, M, N, K):
     torch.testing.assert_close(got, ref, rtol=2e-3, atol=2e-3 * ref.abs().max().item())
 
 
-@pytest.mark.parametrize("form", ["XCP_NT_4W", "XCP_NT_8W", "XCP_NT_KHALF"])
 @pytest.mark.parametrize("M,N,K,stats", [(92416, 736, 736, True), (92416, 736, 736, False), (256 * 100 + 7, 768, 200, True),
                                          (256 * 100 + 7, 768, 392, False), (256 * 300 + 5, 512, 128, False),
                                          (256 * 100 + 7, 736, 728, True)])
-def test_gemm_nt_half_tiles_bitwise(ops, gpu, monkeypatch, M, N, K, stats, form):
-    """Forms of the persistent kernel selected by a switch (the name dates from the half-tile form, since
-    removed with the two-K-tile prefetch form).  XCP_NT_4W=1: the one-wave-per-SIMD kernel (gemm_nt4w_kernel; K = 200 /
-    392 / 736: an odd number of 32-deep steps, padded by a step of zero fragments); XCP_NT_8W=1:
-    gemm_nt8w_kernel on the same ring; XCP_NT_KHALF (0 in the reference run, 1 = the default): a last K-tile
-    with K % 64 in (0, 32] multiplies its first 32-deep half only (K = 200 / 392 / 728 / 736) -- with the
-    static walk (statistics) and with the tile queue (none): output and statistics bits identical to the
-    reference run for every row (the default persistent kernel, same sparse last round on the 128x128
-    kernel)."""
+def test_gemm_nt_khalf_bitwise(ops, gpu, monkeypatch, M, N, K, stats):
+    """XCP_NT_KHALF (0 in the reference run, 1 = the default): a last K-tile of the persistent kernel with
+    K % 64 in (0, 32] multiplies its first 32-deep half only (K = 200 / 392 / 728 / 736) -- with the static
+    walk (statistics) and with the tile queue (none): output and statistics bits identical to the reference
+    run for every row (the default persistent kernel, same sparse last round on the 128x128 kernel)."""
     g = torch.Generator(device=gpu).manual_seed(M + N + K)
     A = torch.randn(M, K, device=gpu, generator=g).bfloat16()
     B = (torch.randn(N, K, device=gpu, generator=g) / K ** 0.5).bfloat16()
     R = ops.nt_stat_rows(M)
     outs = []
     for i in range(3):   # (switched on twice: the tile queue's counter must be reset)
-        monkeypatch.setenv(form, "1" if i else "0")
+        monkeypatch.setenv("XCP_NT_KHALF", "1" if i else "0")
         C = torch.full((M, N), float("nan"), device=gpu, dtype=torch.bfloat16)
         part = torch.full((R, 2, N), float("nan"), device=gpu) if stats else None
         ops.gemm_nt(A, B, C, M, N, K, stats=part, tile=0)
