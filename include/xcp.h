@@ -44,6 +44,10 @@ typedef void* xcp_stream_t; /* hipStream_t */
  * (sum, sum^2) of the stored C columns (BatchNorm batch statistics).
  * gmode: 0 dense rows, 1 strided (skip conv, stride gS), 2 im2col 3x3 p0,
  *        3 transposed im2col (conv input gradient); gC = channels per tap.
+ *        XCP_EINVAL (before any launch) unless the geometry is addressable inside the frames:
+ *        every extent positive; M whole frames of gOH x gOW rows (mode 3: gH x gW);
+ *        mode 1: (gOH - 1) gS <= gH - 1, (gOW - 1) gS <= gW - 1, K <= lda;
+ *        mode 2: gOH + 2 <= gH, gOW + 2 <= gW.  (xcp_gemm_tn: the same, on ldx.)
  * tile: 0 = automatic (256x256 8-wave kernel for dense bf16 with >= 256 output tiles and
  *       K >= 384, or outputs >= 256 wide and K >= 128 -- its persistent form, one workgroup
  *       per CU walking the tiles, with a less than 3/4 full last round of tiles sent to the

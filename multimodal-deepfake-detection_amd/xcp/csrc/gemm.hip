@@ -1776,6 +1776,23 @@ int nt_tq_slot(hipStream_t st) {
   slots.emplace_back(dev, st);
   return (int)slots.size();
 }
+
+// A gather whose geometry cannot be addressed inside the frames the caller describes reads out of bounds
+// (invisibly in the values): M rows must be whole frames of the row space (OH x OW, mode 3: H x W), the
+// last sampled pixel (mode 1) / the last tap (mode 2) must lie inside H x W, and a mode-1 row of K
+// elements inside its pitch.
+bool gather_ok(int gmode, int M, int K, long ld, int gH, int gW, int gOH, int gOW, int gS) {
+  if (gmode == 0) return true;
+  if (gH <= 0 || gW <= 0 || gOH <= 0 || gOW <= 0) return false;
+  const long frame = gmode == 3 ? (long)gH * gW : (long)gOH * gOW;
+  if (M % frame) return false;
+  if (gmode == 1) {
+    const long s = gS > 0 ? gS : 1;
+    return (gOH - 1) * s <= gH - 1 && (gOW - 1) * s <= gW - 1 && K <= ld;
+  }
+  if (gmode == 2) return (long)gOH + 2 <= gH && (long)gOW + 2 <= gW;
+  return true;
+}
 }  // namespace
 
 extern "C" {
@@ -1787,6 +1804,7 @@ int xcp_gemm_nt(int dtype, const void* A, long lda, const void* B, long ldb, voi
   if ((K % 8) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return XCP_EINVAL;
   if (gmode < 0 || gmode > 3 || (gmode >= 2 && (gC % 8 || gC * 9 != K))) return XCP_EINVAL;
   if (tile < 0 || tile > 4) return XCP_EINVAL;
+  if (!gather_ok(gmode, M, K, lda, gH, gW, gOH, gOW, gS)) return XCP_EINVAL;
   NTArgs a{A, lda, B, ldb, C, ldc, M, N, K, stats, Gather{gmode, gH, gW, gOH, gOW, gS > 0 ? gS : 1, gC}};
   a.khalf = nt_khalf() ? 1 : 0;
   if (nt_big(dtype, gmode, M, N, K, tile)) {
@@ -1896,6 +1914,7 @@ int xcp_gemm_tn(int dtype, const void* G, long ldg, const void* X, long ldx, flo
   if ((K % 8) || (N % 8) || (ldg % 8) || (ldx % 8)) return XCP_EINVAL;
   if (gmode < 0 || gmode > 2 || (gmode == 2 && (gC % 8 || gC * 9 != K))) return XCP_EINVAL;
   if (tile < 0 || tile > 2) return XCP_EINVAL;
+  if (!gather_ok(gmode, M, K, ldx, gH, gW, gOH, gOW, gS)) return XCP_EINVAL;
   TNArgs a{G, ldg, X, ldx, P, M, N, K, S, rows_per_split, Gather{gmode, gH, gW, gOH, gOW, gS > 0 ? gS : 1, gC}};
   if (tn_big(dtype, gmode, N, K, tile)) {
     if (rows_per_split % 32) return XCP_EINVAL;

@@ -46,6 +46,11 @@ test_gpu_elementwise_stem_bn.py, which judges the kernels' outputs on the CPU: t
 F.conv2d / conv2d_weight there.  Two more allowances are derived next to their references: the split-bf16
 products of the conv1 row kernels (conv1_ref) and the per-output rounding counts of the finalize kernels
 (bn_finalize_ref, bn_bwd_finalize_ref; judged by assert_within, since their bounds are not sums of n terms).
+
+The gathered GEMMs and the split-K slabs (test_gpu_elementwise_gather.py) need no new bound: gather_rows
+materialises the gathered operand by slicing, gemm_nt_ref / gemm_tn_ref give (ref64, abs_terms) with n = K
+(n = the split's rows for a slab, n <= 128 for a stats row), and weight_grad_extra counts the roundings of
+the slab reduction.
 """
 import torch
 import torch.nn.functional as F
@@ -237,6 +242,94 @@ def gemm_tn_ref(G, X):
     return G.double().t() @ X.double(), G.double().abs().t() @ X.double().abs()
 
 
+def gather_rows(x, mode, geom):
+    """The gathered GEMM operand as a dense [M, K] tensor (x's dtype), by slicing the NHWC tensor: the header of
+    `Gather` in csrc/gemm.hip restated without its index arithmetic.  geom = (H, W, OH, OW, S, Cg), the gather
+    tuple the ops take after the mode; x holds the K = C channels that are read (a wider pitch is sliced off by
+    the caller).
+      mode 1  x [N,H,W,C]:   row (n, oh, ow) = pixel (n, oh S, ow S); K = C
+      mode 2  x [N,H,W,C]:   row (n, oh, ow), column tap C + c = pixel (n, oh + ky, ow + kx), tap = 3 ky + kx; K = 9 C
+      mode 3  x [N,OH,OW,C]: row (n, h, w) over H x W, column tap C + c = pixel (n, h - ky, w - kx) of the OH x OW
+              frame, zero outside it; K = 9 C"""
+    H, W, OH, OW, S, Cg = geom
+    N, C = x.shape[0], x.shape[3]
+    if mode == 1:
+        assert x.shape[1:3] == (H, W)
+        rows = x[:, ::S, ::S]
+        assert rows.shape[1:3] == (OH, OW), (rows.shape, geom)
+        return rows.reshape(N * OH * OW, C)
+    assert Cg == C and (OH, OW) == (H - 2, W - 2), geom
+    if mode == 2:
+        assert x.shape[1:3] == (H, W)
+        return torch.cat([x[:, ky:ky + OH, kx:kx + OW] for ky in range(3) for kx in range(3)], 3).reshape(-1, 9 * C)
+    assert mode == 3 and x.shape[1:3] == (OH, OW)
+    p = F.pad(x, (0, 0, 2, 2, 2, 2))                      # p[h + 2, w + 2] = x[h, w], zero outside
+    return torch.cat([p[:, 2 - ky:2 - ky + H, 2 - kx:2 - kx + W] for ky in range(3) for kx in range(3)],
+                     3).reshape(-1, 9 * C)
+
+
+def nt_stats_ref(C, rows=128):
+    """gemm_nt's BN partial sums: row r = (sum, sum of squares) over the STORED C rows [128 r, 128 r + 128) below M
+    -> (ref64 [R,2,N], abs_terms), n <= 128 (a bf16 square is exact in fp32; an fp32 one is the term's one
+    product rounding)"""
+    M, N = C.shape
+    R = (M + rows - 1) // rows
+    Cd = torch.zeros(R * rows, N, dtype=torch.float64, device=C.device)
+    Cd[:M] = C.double()
+    Cd = Cd.view(R, rows, N)
+    q = (Cd * Cd).sum(1)
+    return torch.stack([Cd.sum(1), q], 1), torch.stack([Cd.abs().sum(1), q], 1)
+
+
+def judge_gathered_nt(C, part, ref, ab, K, tag=""):
+    """What both files assert of a gathered NT product (bf16 C: a bf16 neighbour, >= 99 % nearest, nothing excluded
+    -- these kernels have no ReLU mask; fp32 C: the fp32-sum bound) and of its partial sums (part, or None)
+    -> {"worst", ["nearest", "excluded",] ["stats"]}"""
+    if C.dtype == torch.bfloat16:
+        st = assert_bf16_stored(C, ref, ab, K, nearest_floor=0.99, exclude=None, tag=tag)
+        assert st["excluded"] == 0 and st["nearest"] >= 0.99
+    else:
+        st = assert_f32_sum(C, ref, ab, K, tag=tag)
+    if part is not None:
+        sref, sabs = nt_stats_ref(C)
+        st["stats"] = assert_f32_sum(part, sref, sabs, 128, tag=tag + " stats")["worst"]
+    return st
+
+
+def tn_splits(M, rps):
+    """[(mbeg, mend)] of xcp_gemm_tn's S = ceil(M / rps) row splits"""
+    return [(b, min(M, b + rps)) for b in range(0, M, rps)]
+
+
+def tn_rows_per_split_128(M, N, K):
+    """xcp_gemm_tn_rows_per_split for the 128x128 kernel (every fp32 or gathered call), restated: about 1024
+    workgroups, splits of 256 rows or more, rounded up to 32 (the GPU file asserts it equals the library's)"""
+    cdiv = lambda a, b: -(-a // b)
+    S = max(1, min(1024 // (cdiv(N, 128) * cdiv(K, 128)), cdiv(M, 256)))
+    return cdiv(cdiv(M, S), 32) * 32
+
+
+def gemm_tn_slabs_ref(G, X, rps):
+    """P[s] = G[mbeg:mend]^T X[mbeg:mend] -> (ref64 [S,N,K], abs_terms, n [S,1,1] = the rows of split s)"""
+    Gd, Xd = G.double(), X.double()
+    sp = tn_splits(G.shape[0], rps)
+    ref = torch.stack([Gd[b:e].t() @ Xd[b:e] for b, e in sp])
+    ab = torch.stack([Gd[b:e].abs().t() @ Xd[b:e].abs() for b, e in sp])
+    n = torch.tensor([e - b for b, e in sp], dtype=torch.float64, device=G.device).view(-1, 1, 1)
+    return ref, ab, n
+
+
+REDUCE_LEVELS = 2         # ops.reduce_slabs: fp64 sums of the slabs rounded to fp32 once per level, two levels at most
+
+
+def weight_grad_extra(ab, base=None):
+    """What ops.weight_grad's slab reduction adds to the (M + 2) 2^-24 abs_terms of the slabs' own sums: one fp32
+    rounding per reduction level, and for the accumulate form (base) one fp32 addition.  |value| <= abs_terms."""
+    if base is None:
+        return ab * (REDUCE_LEVELS * U32)
+    return (ab + base.double().abs()) * ((REDUCE_LEVELS + 1) * U32)
+
+
 def unit_dy(G, Y, coef):
     """csrc/unitbwd.hip stage_tile: dY = bf16(fmaf(alpha, G, fmaf(bcoef, Y, delta))) -> (dY bf16, flip fp64)"""
     CO = G.shape[1]
@@ -266,6 +359,24 @@ GEMM_NT_SHAPES = [(256, 256, 32, 32), (1000, 728, 728, 728), (300, 2048, 1536, 1
                   (513, 264, 40, 40), (4100, 1024, 728, 1456)]
 GEMM_TN_SHAPES = [(229, 256, 264), (33, 512, 2048), (300, 2048, 1536)]
 UNIT_BWD_SHAPES = [(M, CO, CI) for M in (453, 1000) for CO, CI in ((128, 128), (128, 64), (256, 128), (256, 256))]
+# gather mode 1 (strided 1x1 conv): N, H, W, Cin, Cout, lda, S
+GATHER1_SHAPES = [(3, 37, 37, 256, 728, 256, 2),     # 1083 rows: 9 M-tiles, the last of 59 rows; 6 N-tiles, the last ragged
+                  (2, 19, 20, 728, 1024, 736, 2),    # K = 11 * 64 + 24, pitch wider than K, even W: the last column never sampled
+                  (2, 10, 7, 8, 8, 8, 2),            # one 16-byte bf16 chunk per row
+                  (1, 1, 1, 64, 64, 64, 2),          # M = 1
+                  (2, 11, 8, 40, 24, 48, 3),         # stride 3: 4 x 3 of 11 x 8, pitch 48
+                  (2, 5, 9, 72, 136, 72, 1)]         # stride 1: bitwise the dense call
+# gather modes 2 / 3 (im2col of the 3x3 valid conv and its transpose): N, H, W, gC (K = 9 gC)
+IM2COL_SHAPES = [(2, 21, 19, 32),     # K = 288 = 4 * 64 + 32: a half-filled last K-stage (bf16)
+                 (1, 3, 3, 32),       # one output pixel (mode 2); every pixel sees exactly one tap (mode 3)
+                 (3, 5, 40, 32),      # 114-pixel frames: the M-tiles span frames
+                 (5, 6, 7, 32),       # mode 2: five 20-pixel frames inside one 128-row tile
+                 (2, 21, 19, 8),      # K = 72: each 16-byte bf16 chunk is another tap's whole channel set
+                 (2, 21, 19, 64)]     # K = 576
+IM2COL_COUT = {2: 64, 3: 32}          # the engine's output widths: conv2 forward, its input gradient
+# dense split-K slabs: (M, N, K) x (tile, rows_per_split): 4 to 10 splits, the last one ragged
+TN_SLAB_SHAPES = [(229, 256, 264), (300, 512, 256)]
+TN_SLAB_FORMS = [(1, 32), (1, 64), (2, 64)]
 
 
 def dw_staged_bf16(W):
@@ -289,6 +400,50 @@ def gemm_nt_inputs(M, N, K, lda):
     Abuf = torch.randn(M, lda, generator=g).bfloat16()
     B = (torch.randn(N, K, generator=g) / K ** 0.5).bfloat16()
     return Abuf, B
+
+
+def gemm_tn_inputs(M, N, K, dtype=torch.bfloat16):
+    g = torch.Generator().manual_seed(M + N)
+    return torch.randn(M, N, generator=g).to(dtype), torch.randn(M, K, generator=g).to(dtype)
+
+
+def gather1_inputs(shape, dtype):
+    """A strided 1x1 conv as the gathered GEMMs take it.  A [N,H,W,lda] is NaN wherever the gather must not
+    read: the unsampled pixels and the pitch columns [K, lda).  B [Cout,K] the forward's weights (K^-1/2), G
+    [M,Cout] the weight gradient's output gradient; signed data."""
+    N, H, W, K, Cout, lda, S = shape
+    g = torch.Generator().manual_seed(7 * N + 31 * H + W + K + Cout + 1000 * S)
+    OH, OW = (H - 1) // S + 1, (W - 1) // S + 1
+    A = torch.randn(N, H, W, lda, generator=g)
+    unread = torch.ones(N, H, W, lda, dtype=torch.bool)
+    unread[:, ::S, ::S, :K] = False
+    A[unread] = float("nan")
+    M = N * OH * OW
+    return {"A": A.to(dtype), "B": (torch.randn(Cout, K, generator=g) / K ** 0.5).to(dtype),
+            "G": torch.randn(M, Cout, generator=g).to(dtype), "M": M, "N": Cout, "K": K, "ld": lda,
+            "geom": (H, W, OH, OW, S, 0), "gather": (1, H, W, OH, OW, S, 0), "unread": int(unread.sum())}
+
+
+def im2col_inputs(shape, mode, dtype):
+    """The 3x3 valid conv gC -> 64 as an im2col GEMM (mode 2: A the input [N,H,W,gC], M = N OH OW rows, G the
+    weight gradient's output gradient) or its input gradient (mode 3: A the output gradient [N,OH,OW,gC] -> 32
+    channels, M = N H W rows); B [Cout, 9 gC], k = tap gC + c."""
+    N, H, W, gC = shape
+    g = torch.Generator().manual_seed(7 * N + 31 * H + W + gC + 1000 * mode)
+    OH, OW = H - 2, W - 2
+    K, Cout = 9 * gC, IM2COL_COUT[mode]
+    M = N * OH * OW if mode == 2 else N * H * W
+    A = torch.randn((N, H, W, gC) if mode == 2 else (N, OH, OW, gC), generator=g)
+    return {"A": A.to(dtype), "B": (torch.randn(Cout, K, generator=g) / K ** 0.5).to(dtype),
+            "G": torch.randn(M, Cout, generator=g).to(dtype), "M": M, "N": Cout, "K": K, "ld": gC,
+            "geom": (H, W, OH, OW, 1, gC), "gather": (mode, H, W, OH, OW, 1, gC)}
+
+
+def gathered(d):
+    """the dense [M, K] operand of a gather1_inputs / im2col_inputs case; it holds none of A's NaNs"""
+    X = gather_rows(d["A"][..., :d["K"]] if d["gather"][0] == 1 else d["A"], d["gather"][0], d["geom"])
+    assert X.shape == (d["M"], d["K"]) and not torch.isnan(X).any()
+    return X
 
 
 # ------------------------------------------------------------------ element-wise BN kernels, pools (csrc/bn.hip)

@@ -12,6 +12,11 @@ The second half does the same for the stem convolutions and the BatchNorm statis
 (test_gpu_elementwise_stem_bn.py): the split-bf16 allowance of the conv1 row kernels is shown to be enough by
 an emulation that forms hi / lo with .bfloat16() and adds the product groups in fp32; the finalize bounds by
 the kernels' fp64 expression with the partial rows summed in another order and the outputs cast to fp32.
+
+The third part serves test_gpu_elementwise_gather.py: gather_rows against torch's own convolutions, fp32
+emulations of the gathered NT products, their stats rows, the split-K slabs and the slab reduction in two
+orders, and chunk-sized planted defects (a chunk from the neighbouring pixel, a wrapped tap, a border tap that
+is not zero, a row counted in two slabs or in none, a stats row counting a stored row twice).
 """
 import pytest
 import torch
@@ -648,3 +653,234 @@ def test_sharp_shift_from_the_neighbouring_channels_mean():
     torch.testing.assert_close(bad["shift"].double(), ref["shift"][0], rtol=1e-4, atol=1e-3)
     with pytest.raises(AssertionError, match="outside the fp32 bound"):
         E.assert_within(bad["shift"], *ref["shift"], tag="shift")
+
+
+# ================================================================== gathered GEMMs and split-K slabs
+GATHER_CASES = [(1, s) for s in E.GATHER1_SHAPES] + [(m, s) for m in (2, 3) for s in E.IM2COL_SHAPES]
+TN_GATHER_CASES = [c for c in GATHER_CASES if c[0] != 3]      # xcp_gemm_tn gathers in modes 0 to 2
+
+
+def gather_case(mode, shape, dt):
+    return E.gather1_inputs(shape, dt) if mode == 1 else E.im2col_inputs(shape, mode, dt)
+
+
+@pytest.mark.parametrize("mode,shape", GATHER_CASES, ids=str)
+def test_gather_rows_against_torch_convs(mode, shape):
+    """gather_rows (slices) times the weights equals fp64 F.conv2d(stride=S) / F.conv2d / F.conv_transpose2d:
+    two independent statements of the operand, to fp64 rounding.  (The NaNs of the mode-1 frame become 1e3 for
+    torch's conv: `gathered` has shown that the slices hold none of them.)"""
+    d = gather_case(mode, shape, FP)
+    H, W, OH, OW, S, gC = d["geom"]
+    N, K, Co = shape[0], d["K"], d["N"]
+    Bd = d["B"].double()
+    got = E.gathered(d).double() @ Bd.t()
+    x = d["A"].double().permute(0, 3, 1, 2)
+    if mode == 1:
+        want = F.conv2d(torch.nan_to_num(x[:, :K], nan=1e3), Bd.view(Co, K, 1, 1), stride=S)
+    elif mode == 2:
+        want = F.conv2d(x, Bd.view(Co, 3, 3, gC).permute(0, 3, 1, 2))
+    else:
+        want = F.conv_transpose2d(x, Bd.view(Co, 3, 3, gC).permute(3, 0, 1, 2))
+    assert want.shape[0] * want.shape[2] * want.shape[3] == d["M"]
+    torch.testing.assert_close(got.view(N, *want.shape[2:], Co).permute(0, 3, 1, 2), want, rtol=0, atol=1e-12)
+
+
+def test_mode3_zero_taps():
+    """at (1, 3, 3) every pixel of the 3 x 3 frame sees the single gradient pixel through exactly one tap"""
+    d = E.im2col_inputs((1, 3, 3, 32), 3, FP)
+    X = E.gathered(d).view(9, 9, 32)
+    for p in range(9):
+        assert [t for t in range(9) if X[p, t].abs().sum() > 0] == [p] and torch.equal(X[p, p], d["A"][0, 0, 0])
+
+
+def emu_nt(A, B, order, dt):
+    """fp32 products and sums in two orders, stored in dt"""
+    A, B = A.float(), B.float()
+    if order == 0:
+        return (A @ B.t()).to(dt)
+    h = A.shape[1] // 2
+    return ((A[:, h:] @ B[:, h:].t()) + (A[:, :h] @ B[:, :h].t())).to(dt)
+
+
+def emu_nt_stats(C, order, twice=None):
+    """fp32 (sum, sum of squares) of the stored rows of each 128-row tile, the rows forward or reversed;
+    twice: the planted defect, that row of the last tile added once more"""
+    out = []
+    for r in range(0, C.shape[0], 128):
+        t = C[r:r + 128].float()
+        if twice is not None and r + 128 >= C.shape[0]:
+            t = torch.cat([t, C[twice:twice + 1].float()])
+        if order:
+            t = t.flip(0)
+        acc = torch.zeros(2, C.shape[1])
+        for row in t:                      # one fp32 addition per row, the square rounded to fp32 first
+            acc[0] = acc[0] + row
+            acc[1] = acc[1] + row * row
+        out.append(acc)
+    return torch.stack(out)
+
+
+def emu_tn_slabs(G, X, rps, order):
+    out = []
+    for b, e in E.tn_splits(G.shape[0], rps):
+        g, x = G[b:e].float(), X[b:e].float()
+        if order:
+            h = (e - b) // 2
+            out.append(g[h:].flip(0).t() @ x[h:].flip(0) + g[:h].t() @ x[:h])
+        else:
+            out.append(g.t() @ x)
+    return torch.stack(out)
+
+
+def emu_reduce(P, base=None):
+    """ops.reduce_slabs: the slabs summed in fp64 and rounded once; accumulate: one fp32 addition"""
+    s = P.double().sum(0).float()
+    return s if base is None else base + s
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("dt", [BF, FP], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("mode,shape", GATHER_CASES, ids=str)
+def test_sound_gathered_nt(mode, shape, dt, order):
+    d = gather_case(mode, shape, dt)
+    X = E.gathered(d)
+    ref, ab = E.gemm_nt_ref(X, d["B"])
+    out = emu_nt(X, d["B"], order, dt)
+    E.judge_gathered_nt(out, emu_nt_stats(out, order), ref, ab, d["K"])
+
+
+def test_rows_per_split_restated():
+    """the 128x128 kernel's own split: ceil(M / 256) splits at most (five of the 1083 rows, one of the 200)"""
+    assert E.tn_rows_per_split_128(1083, 728, 256) == 224 and E.tn_rows_per_split_128(200, 1024, 728) == 224
+    assert E.tn_rows_per_split_128(5000, 128, 64) == 256 and E.tn_rows_per_split_128(1, 8, 8) == 32
+    assert E.tn_rows_per_split_128(92416, 728, 728) == 3328          # 28 splits of 36 tiles: 1008 workgroups
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("dt", [BF, FP], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("M,N,K", E.TN_SLAB_SHAPES)
+def test_sound_dense_slabs(M, N, K, dt, order):
+    G, X = E.gemm_tn_inputs(M, N, K, dt)
+    for rps in sorted({r for _, r in E.TN_SLAB_FORMS}):
+        ref, ab, n = E.gemm_tn_slabs_ref(G, X, rps)
+        assert 4 <= len(n) <= 10 and n[-1] < rps           # several splits, the last one ragged
+        E.assert_f32_sum(emu_tn_slabs(G, X, rps, order), ref, ab, n)
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("dt", [BF, FP], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("mode,shape", TN_GATHER_CASES, ids=str)
+def test_sound_gathered_slabs_and_weight_grad(mode, shape, dt, order):
+    d = gather_case(mode, shape, dt)
+    X, G, M = E.gathered(d), d["G"], d["M"]
+    assert M <= 1083
+    wref, wab = E.gemm_tn_ref(G, X)
+    base = torch.randn(d["N"], d["K"], generator=torch.Generator().manual_seed(M))
+    for rps in (E.tn_rows_per_split_128(M, d["N"], d["K"]), 32):
+        ref, ab, n = E.gemm_tn_slabs_ref(G, X, rps)
+        P = emu_tn_slabs(G, X, rps, order)
+        E.assert_f32_sum(P, ref, ab, n)
+        E.assert_f32_sum(emu_reduce(P), wref, wab, M, extra=E.weight_grad_extra(wab))
+        E.assert_f32_sum(emu_reduce(P, base), wref + base.double(), wab, M, extra=E.weight_grad_extra(wab, base))
+
+
+# ------------------------------------------------------------------ sharp: gathered operands, slabs, stats rows
+def nt_defect(mode, shape, plant):
+    """(bad, ref, ab, K): the bf16 emulation of a gathered NT case with `plant(X, d)` applied to the dense
+    operand; the clean emulation passes the element-wise measure"""
+    d = gather_case(mode, shape, BF)
+    X = E.gathered(d)
+    ref, ab = E.gemm_nt_ref(X, d["B"])
+    E.judge_gathered_nt(emu_nt(X, d["B"], 0, BF), None, ref, ab, d["K"])
+    Xb = X.clone()
+    plant(Xb, d)
+    assert (Xb != X).any(1).sum() == 1 and (Xb != X).sum() <= 8          # one chunk of one row
+    return emu_nt(Xb, d["B"], 0, BF), ref, ab, d["K"]
+
+
+def test_sharp_mode1_chunk_from_the_pixel_to_the_right():
+    """one 16-byte chunk (8 channels) of one output row read one pixel to the right of the sampled one -- an
+    unsampled pixel, so the data is given there first.  1 row of 1083, 8 of 256 channels: 0.008 norm-wise."""
+    n, oh, ow, c0 = 1, 7, 11, 104
+
+    def plant(X, d):
+        H, W, OH, OW, S, _ = d["geom"]
+        right = torch.randn(8, generator=torch.Generator().manual_seed(5)).bfloat16()
+        assert torch.isnan(d["A"][n, oh * S, ow * S + 1, c0:c0 + 8]).all()        # the neighbour is not sampled
+        X[(n * OH + oh) * OW + ow, c0:c0 + 8] = right
+    caught(*nt_defect(1, E.GATHER1_SHAPES[0], plant))
+
+
+def test_sharp_mode2_last_tap_wraps_into_the_next_row():
+    """the last pixel of a frame's row: one chunk of its tap (ky, kx) = (2, 2), column W - 1, taken from column 0
+    of the row below, where W would be.  gC = 64: 8 of 576 columns of 1 row of 646."""
+    n, oh, c0 = 1, 3, 40
+
+    def plant(X, d):
+        H, W, OH, OW, S, gC = d["geom"]
+        X[(n * OH + oh) * OW + OW - 1, 8 * gC + c0:8 * gC + c0 + 8] = d["A"][n, oh + 3, 0, c0:c0 + 8]
+    caught(*nt_defect(2, (2, 21, 19, 64), plant))
+
+
+def test_sharp_mode3_corner_tap_from_the_neighbouring_frame():
+    """pixel (0, 0) of frame 1 sees the gradient through tap (0, 0) alone; one chunk of its tap (1, 0) -- gradient
+    row -1 -- taken from where that index lands, the last row of frame 0, instead of zero"""
+    c0 = 16
+
+    def plant(X, d):
+        H, W, OH, OW, S, gC = d["geom"]
+        assert (X[H * W, gC:] == 0).all()
+        X[H * W, 3 * gC + c0:3 * gC + c0 + 8] = d["A"][0, OH - 1, 0, c0:c0 + 8]
+    caught(*nt_defect(3, (2, 21, 19, 32), plant))
+
+
+@pytest.mark.parametrize("dt,thr,scale", [(BF, 1e-3, 2.0 ** -6), (FP, 1e-5, 2.0 ** -13)], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("defect", ["twice", "dropped"])
+def test_sharp_split_boundary_row(defect, dt, thr, scale):
+    """The last row of a split counted in the next slab as well, or in neither, on the stride-2 skip conv's
+    weight gradient (1083 rows, 34 splits of 32).  A whole row of ordinary size is 0.03 of dW's norm and the old
+    measure (rel_err < 1e-3 bf16, 1e-5 fp32 on ops.weight_grad's output) sees it; gradients of a training step
+    span orders of magnitude over the pixels, so the row is given a gradient of 2^-6 (2^-13) of the others'.
+    The old measure passes; the slab it lands in (or is missing from) leaves the bound of its 32 rows' sum.  The
+    bound of the whole sum (n = 1083) still holds the fp32 defect: the slabs are what sees it."""
+    d = gather_case(1, E.GATHER1_SHAPES[0], dt)
+    X, M, rps, s = E.gathered(d), d["M"], 32, 20
+    m = (s + 1) * rps - 1                                   # the last row of split s
+    G = d["G"].clone()
+    G[m] = (G[m].float() * scale).to(dt)
+    ref, ab, n = E.gemm_tn_slabs_ref(G, X, rps)
+    P = emu_tn_slabs(G, X, rps, 0)
+    E.assert_f32_sum(P, ref, ab, n)
+    term = G[m].float()[:, None] * X[m].float()[None, :]
+    bad = P.clone()
+    if defect == "twice":
+        bad[s + 1] += term
+    else:
+        bad[s] -= term
+    wref, wab = E.gemm_tn_ref(G, X)
+    assert rel_err(emu_reduce(bad), wref) < thr
+    with pytest.raises(AssertionError, match="outside the fp32 bound"):
+        E.assert_f32_sum(bad, ref, ab, n)
+    if dt == FP:
+        E.assert_f32_sum(emu_reduce(bad), wref, wab, M, extra=E.weight_grad_extra(wab))
+
+
+def test_sharp_stats_row_counts_a_stored_row_twice():
+    """the ragged last tile (59 rows of 1083) adds its last stored row twice: C itself is untouched, the
+    normalised output the sums lead to passes rel_err < 1e-2, the stats row leaves its fp32 bound"""
+    d = gather_case(1, E.GATHER1_SHAPES[0], BF)
+    X, M = E.gathered(d), d["M"]
+    C = emu_nt(X, d["B"], 0, BF)
+    sref, sabs = E.nt_stats_ref(C)
+    good, bad = emu_nt_stats(C, 0), emu_nt_stats(C, 0, twice=M - 1)
+    E.assert_f32_sum(good, sref, sabs, 128)
+    assert torch.equal(bad[:-1], good[:-1])
+
+    def normalised(part):
+        s = part.double().sum(0)
+        mean = s[0] / M
+        return ((C.double() - mean) / (s[1] / M - mean * mean + 1e-5).sqrt()).bfloat16()
+
+    assert rel_err(normalised(bad).float(), normalised(sref)) < 1e-2
+    with pytest.raises(AssertionError, match="outside the fp32 bound"):
+        E.assert_f32_sum(bad, sref, sabs, 128)
