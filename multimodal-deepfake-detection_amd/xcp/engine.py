@@ -116,34 +116,12 @@ STEM_FUSED = os.environ.get("XCP_STEM_FUSED", "1") != "0"
 # an identity-skip block boundary's BN partial sums from the next block's first depthwise backward
 # (xcp_dw_bwd_resbn) instead of a per-channel reduce pass (XCP_RESBN=1; default off until measured)
 RESBN = os.environ.get("XCP_RESBN", "0") == "1"
-STEM_WGRAD_SIDE = WGRAD_SIDE_STREAM and os.environ.get("XCP_STEM_WGRAD_SIDE", "1") != "0"
-SIDE_PRIO_LOW = os.environ.get("XCP_SIDE_PRIO", "") == "low"
-# BN1's backward coefficients before the side-stream conv2 weight gradient is launched
-# (XCP_STEM_BN1_FIRST=0: after it, the round-2 order; A/B)
-STEM_BN1_FIRST = os.environ.get("XCP_STEM_BN1_FIRST", "1") != "0"
 # conv1's weight gradient forms BN1's backward apply (+ ReLU mask) on load instead of reading a stored
 # dC1 (xcp_conv1_wgrad_bn; XCP_CONV1_BN_FUSED=0: bn_bwd_apply + conv1_wgrad, A/B)
 CONV1_BN_FUSED = os.environ.get("XCP_CONV1_BN_FUSED", "1") != "0"
-# conv2's weight gradient launched on the weight-gradient stream before conv2's input gradient, so it runs
-# beside the dgrad, BN1's coefficients and conv1's weight gradient instead of after them and the backward
-# no longer ends waiting for it (+0.2-0.5 % in two interleaved rounds, profiles/r04_stem_order_ab.txt;
-# XCP_STEM_WGRAD_EARLY=0: after BN1's coefficients)
-STEM_WGRAD_EARLY = os.environ.get("XCP_STEM_WGRAD_EARLY", "1") != "0"
-# BN1's backward finalize in 4-wave workgroups (XCP_FIN_NARROW) while conv2's weight gradient holds every CU on the
-# side stream: the 16-wave workgroup found no SIMD with room for 4 of its waves and waited for the whole weight
-# gradient (144 us per step, profiles/r06_conv3_wgrad_ab.txt).  XCP_STEM_FIN_NARROW=0: the 16-wave form (A/B)
-STEM_FIN_NARROW = os.environ.get("XCP_STEM_FIN_NARROW", "1") != "0"
 # BN1's batch statistics from conv1's forward (xcp_conv1_fwd_stats; XCP_CONV1_STATS_FUSED=0: a per-channel
 # reduce over the stored output, A/B)
 CONV1_STATS_FUSED = os.environ.get("XCP_CONV1_STATS_FUSED", "1") != "0"
-# depthwise weight-gradient slab reductions on the weight-gradient stream (XCP_DW_REDUCE_SIDE=0:
-# on the main stream right after each depthwise backward)
-DW_REDUCE_SIDE = WGRAD_SIDE_STREAM and os.environ.get("XCP_DW_REDUCE_SIDE", "1") != "0"
-# one block's weight-gradient slab reductions batched into one or two launches (XCP_REDUCE_BATCH=0:
-# one launch per weight, as they are produced)
-REDUCE_BATCH = os.environ.get("XCP_REDUCE_BATCH", "1") != "0"
-# XCP_NT_ONESHOT=1: the big pointwise GEMMs on the one-shot 256x256 kernel instead of its
-# persistent form (gemm.hip tile 4 vs 0; A/B); XCP_NT_TILE=<t> pins any gemm.hip tile choice for them
 # block1's units (147^2, 64 -> 128 and 128 -> 128) run depthwise + pointwise + BN sums as one kernel
 # (csrc/sepfwd.hip): the depthwise output goes to the MFMAs through LDS instead of back through HBM
 # (XCP_SEP_FUSED=0: the two kernels; A/B)
@@ -151,24 +129,13 @@ SEP_FUSED = os.environ.get("XCP_SEP_FUSED", "1") != "0"
 # ... from these frame widths on: the kernel computes whole 80-pixel half rows (two for 128 outputs, one
 # for 256) with four barriers each, so on narrow frames most of its work is padding and the per-row
 # barriers dominate (64^2 clips, block1 at 29^2: 848 us per launch against the two kernels' ~300, C4
-# line 1847 -> 2279 clips/s with the two kernels, profiles/r06_c4_ab.txt).  XCP_SEP_NARROW=1: every
-# width the kernel supports (A/B)
-SEP_MIN_W = {128: 0, 256: 0} if os.environ.get("XCP_SEP_NARROW", "0") == "1" else {128: 120, 256: 64}
+# line 1847 -> 2279 clips/s with the two kernels, profiles/r06_c4_ab.txt)
+SEP_MIN_W = {128: 120, 256: 64}
 # the stem conv2 (forward and weight gradient) applies BN1 + ReLU on load instead of reading a
 # materialised relu(bn1(conv1)) (XCP_CONV2_ACTIN=0: bn_act + the plain conv; A/B)
 CONV2_ACT_ON_LOAD = os.environ.get("XCP_CONV2_ACTIN", "1") != "0"
-# XCP_WGRAD_FIRST=1: a unit's pointwise weight gradient launched on the side stream before its input
-# gradient, so the two overlap (A/B; +0.40 % on one box, -0.17 % on another: profiles/r05_wgrad_first_ab.txt;
-# off: the side stream waits for the input gradient)
-WGRAD_FIRST = os.environ.get("XCP_WGRAD_FIRST", "0") == "1"
-# XCP_WGRAD_DEFER=1: a unit's pointwise weight gradient is launched on the side stream after the NEXT unit's
-# input gradient instead of its own, so it runs beside the memory-bound depthwise backward / BN apply that
-# follow rather than beside the next input-gradient GEMM (A/B)
-WGRAD_DEFER = os.environ.get("XCP_WGRAD_DEFER", "0") == "1"
-# XCP_SKIP_WGRAD_LATE=1: a block's skip-conv weight gradient launched on the side stream after the block's
-# units instead of before them (A/B: off keeps it beside the block's own depthwise backward)
-SKIP_WGRAD_LATE = os.environ.get("XCP_SKIP_WGRAD_LATE", "0") == "1"
-NT_TILE = int(os.environ.get("XCP_NT_TILE", "4" if os.environ.get("XCP_NT_ONESHOT", "0") == "1" else "0"))
+# XCP_NT_TILE=<t> pins a gemm.hip tile choice for the big pointwise GEMMs (0: the library's own)
+NT_TILE = int(os.environ.get("XCP_NT_TILE", "0"))
 # Channel pitch of the 728-channel flow (block3 .. block12): 736, so every pixel row starts on a
 # 64-B (bf16) / 128-B (fp32) boundary.  The 8 padding channels are zero throughout: zero rows /
 # columns in the packed weights, zero BN scale / shift / backward coefficients.  XCP_PAD_728=0
@@ -214,11 +181,7 @@ class XceptionEngine:
     def _side_stream(self, dev):
         st = getattr(self, "_side", None)
         if st is None or st.device != dev:
-            # XCP_SIDE_PRIO=low: the weight-gradient stream at the least priority the device offers
-            # (below the default stream's when the range has one), so the dispatcher prefers the
-            # main stream's workgroups (A/B; the default creates it at the default priority)
-            prio = torch.cuda.Stream.priority_range()[0] if SIDE_PRIO_LOW else 0
-            st = self._side = torch.cuda.Stream(dev, priority=prio)
+            st = self._side = torch.cuda.Stream(dev)
         return st
 
     def bn_training(self):
@@ -548,18 +511,16 @@ class XceptionEngine:
         # Main-stream tensors the side stream reads are kept referenced here until the main
         # stream has waited for the side stream (end of this backward); freeing them after that
         # point is stream-ordered, so the caching allocator may hand them out again at once.
-        # (record_stream instead defers their reuse until the side stream's work has actually
-        # run on the GPU; with the host a step or more ahead of the GPU that kept every step's
+        # (Recording them on the side stream with the allocator instead defers their reuse until
+        # that stream's work has actually run on the GPU; with the host a step or more ahead that kept every step's
         # backward temporaries unusable and the allocator mapped fresh device memory every step:
         # 140-170 hipMallocs in 20 timed steps and 149 GB reserved for 25.6 GB in use.)
         keep = []
         # the weight-gradient slab reductions of one block (pointwise split-K slabs, depthwise
-        # partials) go out together in one or two launches when the block is done (REDUCE_BATCH)
-        rbatch = ops.ReduceBatch() if REDUCE_BATCH else None
+        # partials) go out together in one or two launches when the block is done
+        rbatch = ops.ReduceBatch()
 
-        deferred = []   # (WGRAD_DEFER) the last unit's weight gradient, launched after the next input gradient
-
-        def wgrad(G, X, M, Nn, K, name, shape, defer=False, **kw):
+        def wgrad(G, X, M, Nn, K, name, shape, **kw):
             """dW[Nn][K] = G^T X (logical channels; G / X at their channel pitches)"""
             if not needed(name):
                 return
@@ -569,29 +530,15 @@ class XceptionEngine:
             if side is None:
                 ops.weight_grad(G, X, M, Nn, K, dst, accumulate=acc, batch=rbatch, **kw)
                 return
-            if defer:
-                flush_deferred()
-                deferred.append((G, X, M, Nn, K, dst, acc, kw))
-                keep.extend((G, X))
-                return
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 ops.weight_grad(G, X, M, Nn, K, dst, accumulate=acc, batch=rbatch, **kw)
             keep.extend((G, X))   # dst: a gradient, referenced by the caller until the end
 
-        def flush_deferred():
-            if deferred:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    for G, X, M, Nn, K, dst, acc, kw in deferred:
-                        ops.weight_grad(G, X, M, Nn, K, dst, accumulate=acc, batch=rbatch, **kw)
-                deferred.clear()
-
         def done():
             """every gradient requested since the last call is enqueued: reduce the block's slabs,
             tell the sink"""
-            flush_deferred()
-            if rbatch is not None and rbatch.jobs:
+            if rbatch.jobs:
                 if side is not None:
                     side.wait_stream(main)   # the depthwise partials come from the main stream
                     with torch.cuda.stream(side):
@@ -641,19 +588,18 @@ class XceptionEngine:
                 ops.unit_bwd(dZ, rec["y"], coef, pk[u.name + ".pwT"], rec["d"], dD, M, u.cout, u.cin, dst, acc)
             else:
                 dY = bn_bwd(u.bn, u.bn_name, dZ, rec["y"], M, u.cout, rec["st"], part)
-                if WGRAD_FIRST:   # the side stream starts on dY before this unit's input gradient (A/B)
-                    wgrad(dY, rec["d"], M, u.cout, u.cin, u.name + ".pointwise.weight", (u.cout, u.cin, 1, 1))
+                # the input gradient, then the weight gradient on the side stream (which waits for the input
+                # gradient: launched before it, or after the next unit's, it measured inside the noise,
+                # profiles/r05_wgrad_first_ab.txt, profiles/r06_wgrad_defer_ab.txt)
                 ops.gemm_nt(dY, pk[u.name + ".pwT"], dD, M, pc(u.cin), pc(u.cout), tile=NT_TILE)
-                if not WGRAD_FIRST:
-                    wgrad(dY, rec["d"], M, u.cout, u.cin, u.name + ".pointwise.weight", (u.cout, u.cin, 1, 1),
-                          defer=WGRAD_DEFER)
+                wgrad(dY, rec["d"], M, u.cout, u.cin, u.name + ".pointwise.weight", (u.cout, u.cin, 1, 1))
             dX = self._empty(M * pc(u.cin))
             dwg, acc = g(u.name + ".conv1.weight", (u.cin, 1, 3, 3)) if needed(u.name + ".conv1.weight") else (None, False)
             bnp = ops.dw_bwd(rec["act"], dD, rec["src"], pk[u.name + ".dw"], rec["sc"], rec["sh"], dX, dwg, N, H, W,
                              pc(u.cin), dRes=dRes, dSkip=dSkip, skip_geom=skip_geom,
                              bn_stats=res_bn[1] if res_bn is not None else prev_st, accumulate=acc,
-                             Cw=u.cin, skip_pre=skip_pre, reduce_stream=side if DW_REDUCE_SIDE else None,
-                             keep=keep, batch=rbatch, res_bn_input=res_bn[0] if res_bn is not None else None)
+                             Cw=u.cin, skip_pre=skip_pre, keep=keep, batch=rbatch,
+                             res_bn_input=res_bn[0] if res_bn is not None else None)
             return dX, (bnp if prev_st is not None or res_bn is not None else None)
 
         # ---- exit flow
@@ -680,14 +626,15 @@ class XceptionEngine:
             dC2 = bn_bwd(m.bn2, "bn2", dX, S["c2"], rows2, 64, S["s2"], part=pre_part)
         else:
             dC2 = bn_bwd(m.bn2, "bn2", dX, S["c2"], rows2, 64, S["s2"], relu=True)   # relu (Xception.py:174) fused
-        def conv2_wgrad(st2):
-            """conv2's weight gradient (from dC2 and a1) on stream st2 (None: the current one)"""
+
+        def conv2_wgrad():
+            """conv2's weight gradient (from dC2 and a1), on the side stream when there is one"""
             if not needed("conv2.weight"):
                 return
-            if st2 is not None:
-                st2.wait_stream(main)
+            if side is not None:
+                side.wait_stream(main)
             c2g, acc = g("conv2.weight", (64, 32, 3, 3))   # (allocated on the main stream)
-            with torch.cuda.stream(st2) if st2 is not None else contextlib.nullcontext():
+            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
                 w2g = torch.empty(64 * 288, device=dev, dtype=torch.float32)
                 if S["a1"] is None:   # (conv2 read conv1's output with BN1 + ReLU on load)
                     ops.conv3x3_wgrad(dC2, S["c1"], w2g, N, OH1, OW1, in_scale=S["s1"].scale, in_shift=S["s1"].shift)
@@ -701,30 +648,30 @@ class XceptionEngine:
                     c2g.add_(tmp)
                 else:
                     ops.permute3(w2g, c2g, 64, 9, 32, (0, 2, 1))
-            if st2 is not None:
+            if side is not None:
                 keep.append(dC2)
 
-        st2 = side if STEM_WGRAD_SIDE else None
-        if STEM_WGRAD_EARLY and st2 is not None:   # beside conv2's input gradient (A/B)
-            conv2_wgrad(st2)
+        # With a side stream, conv2's weight gradient is launched on it before conv2's input gradient, so it
+        # runs beside the input gradient, BN1's coefficients and conv1's weight gradient and the backward no
+        # longer ends waiting for it (+0.2-0.5 % in two interleaved rounds, profiles/r04_stem_order_ab.txt).
+        if side is not None:
+            conv2_wgrad()
         dA1 = self._empty(rows1 * 32)
         if self.dtype == torch.bfloat16 and ops.conv3x3_parts(1, N, OH2, OW2) > 0:
             ops.conv3x3(1, dC2, pk["conv2T"], dA1, None, N, OH2, OW2)
         else:
             ops.gemm_nt(dC2, pk["conv2T"], dA1, rows1, 32, 576, lda=64, gather=(3, OH1, OW1, OH2, OW2, 1, 64))
-        # BN1's backward coefficients first (per-channel reduce + finalize on the main stream), then
-        # conv2's weight gradient on the weight-gradient stream beside the rest of the chain (BN1
-        # apply, conv1's weight gradient).  Launched the other way round, the finalize's one
-        # 1024-thread workgroup waited for the side stream's conv2 weight gradient to leave the CUs:
-        # 356 us per step on the main stream (profiles/r03_v3_kernels.txt)
-        # (narrow finalize: conv2's weight gradient holds every CU beside it when launched early)
-        if STEM_BN1_FIRST:
-            coef1 = bn_coef(m.bn1, "bn1", dA1, S["c1"], rows1, 32, S["s1"], None, True,   # relu (Xception.py:170)
-                            narrow=STEM_FIN_NARROW and STEM_WGRAD_EARLY and st2 is not None)
-        if not (STEM_WGRAD_EARLY and st2 is not None):
-            conv2_wgrad(st2)
-        if not STEM_BN1_FIRST:
-            coef1 = bn_coef(m.bn1, "bn1", dA1, S["c1"], rows1, 32, S["s1"], None, True)
+        # BN1's backward coefficients (per-channel reduce + finalize on the main stream).  Beside the side
+        # stream's conv2 weight gradient, which holds every CU, the finalize runs in 4-wave workgroups
+        # (XCP_FIN_NARROW): its one 16-wave (1024-thread) workgroup found no SIMD with room for 4 of its waves
+        # and waited for the whole weight gradient to leave the CUs -- 356 us per step on the main stream
+        # when first seen (profiles/r03_v3_kernels.txt), 144 us with the current weight-gradient kernel
+        # (profiles/r06_conv3_wgrad_ab.txt).  Without a side stream nothing runs beside it: the 16-wave
+        # form, and conv2's weight gradient follows on the main stream.
+        coef1 = bn_coef(m.bn1, "bn1", dA1, S["c1"], rows1, 32, S["s1"], None, True,   # relu (Xception.py:170)
+                        narrow=side is not None)
+        if side is None:
+            conv2_wgrad()
         # conv1's weight gradient and (input_grad) its data gradient, the gradient w.r.t. the frames: both form
         # BN1's backward apply + ReLU mask on load where the fused weight gradient takes the shape (dC1 is
         # never stored), and both read one stored dC1 otherwise
@@ -776,15 +723,13 @@ class XceptionEngine:
         skip_geom = (0, 0, 1)
         if b.skip is not None:
             dYs = bn_bwd(b.skipbn, b.name + ".skipbn", dOut, bs["ys"], Ms, b.cout, bs["sks"])
-
-            def skip_wgrad():
-                if bs["skip_x"] is not None:
-                    wgrad(dYs, bs["skip_x"], Ms, b.cout, b.cin, b.name + ".skip.weight", (b.cout, b.cin, 1, 1))
-                else:
-                    wgrad(dYs, bs["x_in"], Ms, b.cout, b.cin, b.name + ".skip.weight", (b.cout, b.cin, 1, 1),
-                          gather=(1, H, W, OH, OW, b.stride, 0) if b.stride != 1 else (0, 0, 0, 0, 0, 1, 0))
-            if not SKIP_WGRAD_LATE:
-                skip_wgrad()
+            # the skip conv's weight gradient first: on the side stream it runs beside the skip's input gradient
+            # and the block's own depthwise backward (after the units: -0.11 %, profiles/r05_skip_wgrad_late_ab.txt)
+            if bs["skip_x"] is not None:
+                wgrad(dYs, bs["skip_x"], Ms, b.cout, b.cin, b.name + ".skip.weight", (b.cout, b.cin, 1, 1))
+            else:
+                wgrad(dYs, bs["x_in"], Ms, b.cout, b.cin, b.name + ".skip.weight", (b.cout, b.cin, 1, 1),
+                      gather=(1, H, W, OH, OW, b.stride, 0) if b.stride != 1 else (0, 0, 0, 0, 0, 1, 0))
             dXs = self._empty(Ms * pc(b.cin))
             ops.gemm_nt(dYs, pk[b.name + ".skipT"], dXs, Ms, pc(b.cin), pc(b.cout), tile=NT_TILE)
             if b.stride != 1:
@@ -810,8 +755,6 @@ class XceptionEngine:
                                         prev_st=pre, skip_pre=pre is not None, res_bn=res_bn)
                 pre_part = out_part if pre is not None else None
                 prev_part = out_part if res_bn is not None else None
-        if b.skip is not None and SKIP_WGRAD_LATE:
-            skip_wgrad()
         return dZ, pre_part, prev_part
 
 

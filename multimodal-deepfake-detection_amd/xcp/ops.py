@@ -213,18 +213,16 @@ def sep_fwd(act, X, scale, shift, dwt, pw, D, Y, part, N, H, W, cin, cout):
 
 
 def dw_bwd(act, dY, X, Wt, scale, shift, dX, dW_out, N, H, W, C, dRes=None, dSkip=None, skip_geom=(0, 0, 1),
-           bn_stats=None, accumulate=False, Cw=None, skip_pre=False, reduce_stream=None, keep=None, batch=None,
-           res_bn_input=None):
+           bn_stats=None, accumulate=False, Cw=None, skip_pre=False, keep=None, batch=None, res_bn_input=None):
     """Returns (bnpart, P) -- the preceding BN's backward partial sums -- when bn_stats
     (that BN's Stats) is given, else (None, 0).  dW_out receives the weight gradient in the
     nn.Conv2d [C][1][3][3] order (accumulate: added to it; None: not wanted); Cw (default C): channels of the
     weight when C is a padded channel pitch.  skip_pre: dSkip is a gradient of the same
     activation act(X) (it passes the activation mask and enters the BN partial sums).
-    reduce_stream: run the weight-gradient slab reduction there (ordered after this launch);
-    keep: a list that receives the scratch the reduce stream reads, for a caller that holds it
-    until its stream has waited for the reduce stream (otherwise it is record_stream'ed);
-    batch (ReduceBatch): the slab reduction is added to it instead (the caller flushes it after
-    ordering its stream behind this launch, and keeps the scratch alive through ``keep``).
+    batch (ReduceBatch): the weight-gradient slab reduction is added to it instead of launched here
+    (the caller flushes it on this stream or one ordered behind this launch); keep: a list that then
+    receives the scratch that reduction reads, for a caller that flushes on another stream and holds
+    the scratch until this stream has waited for that one.
     res_bn_input (with dRes, no dSkip; bn_stats then the Stats of that BN): the partial sums are
     those of the BN whose output gradient is the final dX (after the residual add) and whose input
     is res_bn_input -- an identity-skip block boundary (xcp_dw_bwd_resbn)."""
@@ -250,17 +248,8 @@ def dw_bwd(act, dY, X, Wt, scale, shift, dX, dW_out, N, H, W, C, dRes=None, dSki
         batch.add(part, P, (Cw or C) * 9, dW_out, accumulate, ld=C * 9)
         if keep is not None:
             keep.append(part)
-    elif reduce_stream is None:
-        reduce_slabs(part, P, (Cw or C) * 9, dW_out, accumulate, ld=C * 9)
     else:
-        reduce_stream.wait_stream(torch.cuda.current_stream(dY.device))
-        with torch.cuda.stream(reduce_stream):
-            reduce_slabs(part, P, (Cw or C) * 9, dW_out, accumulate, ld=C * 9)
-        if keep is not None:
-            keep.append(part)
-        else:
-            part.record_stream(reduce_stream)
-            dW_out.record_stream(reduce_stream)
+        reduce_slabs(part, P, (Cw or C) * 9, dW_out, accumulate, ld=C * 9)
     return bnpart, (P if bnpart is not None else 0)
 
 

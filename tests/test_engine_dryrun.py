@@ -27,9 +27,19 @@ def _fill(ptr, n, acc):
         a[i] = (a[i] if acc else 0.0) + FILL["v"]
 
 
+class _Calls(list):
+    """Entry-point names in call order; ``trace`` has one (stream name, entry point, integer arguments)
+    per call: the stream that was current when the call was made, and the arguments the signature
+    declares as integers (sizes, modes, flags -- no pointers, no floats)."""
+
+    def __init__(self):
+        super().__init__()
+        self.trace = []
+
+
 def install_fake_lib(monkeypatch):
     from xcp import _lib, ops
-    calls = []
+    calls = _Calls()
 
     def fake_call(name, *args):
         sig = _lib.SIGNATURES[name]
@@ -37,6 +47,8 @@ def install_fake_lib(monkeypatch):
         for a, t in zip(args, sig):
             t(a if a is not None else 0)  # raises on an unconvertible argument
         calls.append(name)
+        calls.trace.append((torch.cuda.current_stream().name, name,
+                            tuple(a for a, t in zip(args, sig) if t in (_lib.I, _lib.L, ctypes.c_longlong))))
         if name == "xcp_colreduce_f32":       # (in, S, L, ld, out, G, accumulate, stream): gradient slabs
             _fill(args[4], args[2] * args[5], args[6])
         elif name == "xcp_colreduce_multi":   # (jobs [n][7] = in, out, S, L, ld, G, acc; n; stream)
@@ -81,7 +93,7 @@ def install_fake_lib(monkeypatch):
     monkeypatch.setattr(engine, "WGRAD_SIDE_STREAM", False)   # no HIP streams on the CPU
 
     class _S:
-        cuda_stream = 0
+        cuda_stream, name = 0, "main"
 
     monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _S())
 
@@ -357,8 +369,10 @@ class _FakeEvent:
         self.stream = stream or _FakeStream.current
 
 
-def _install_fake_streams(calls):
-    _FakeStream.log, _FakeStream.calls = [], calls
+def _install_fake_streams(calls, monkeypatch):
+    """torch.cuda's streams and events replaced by the recording stand-ins, through ``monkeypatch`` (pytest's, so a
+    test in this process is undone at its end; a spawned worker passes its own minimal shim)"""
+    _FakeStream.log, _FakeStream.calls, _FakeStream.n = [], calls, 0
     _FakeStream.current = _FakeStream(name="main")
 
     @contextlib.contextmanager
@@ -369,10 +383,115 @@ def _install_fake_streams(calls):
         finally:
             _FakeStream.current = prev
 
-    torch.cuda.Stream = _FakeStream
-    torch.cuda.Event = _FakeEvent
-    torch.cuda.stream = stream
-    torch.cuda.current_stream = lambda *a, **k: _FakeStream.current
+    monkeypatch.setattr(torch.cuda, "Stream", _FakeStream)
+    monkeypatch.setattr(torch.cuda, "Event", _FakeEvent)
+    monkeypatch.setattr(torch.cuda, "stream", stream)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _FakeStream.current)
+
+
+def _xception_step_trace(monkeypatch, side_stream):
+    """one bf16 xception forward + backward at 2x3x71x71 on the fake library and fake streams ->
+    (engine, calls, number of forward calls, wait log)"""
+    import xcp
+    from xcp import engine
+    from Models.Xception import xception
+    calls = install_fake_lib(monkeypatch)
+    monkeypatch.setattr(engine, "WGRAD_SIDE_STREAM", side_stream)
+    _install_fake_streams(calls, monkeypatch)
+    torch.manual_seed(0)
+    m = xception(num_classes=1)
+    with xcp.precision("bf16"):
+        y = m(torch.rand(2, 3, 71, 71))
+        nfwd = len(calls)
+        torch.nan_to_num(y).sum().backward()
+        eng = m._engine()
+    return eng, calls, nfwd, list(_FakeStream.log)
+
+
+def test_default_backward_schedule(monkeypatch):
+    """The one launch order and stream placement of the backbone backward (xception, 2x3x71x71, bf16).
+
+    With the weight-gradient side stream: every pointwise / skip weight-gradient GEMM, every batched slab
+    reduction and the stem conv2 weight gradient (with the reduce and permute that finish it) are on the side
+    stream, each ordered behind the main stream's last launch by a ``side.wait_stream(main)``; everything else
+    is on the main stream.  A unit's weight gradient follows its input gradient, a skip conv's precedes the
+    skip's input gradient, each block's slab reductions go out as one group after the block.  Stem: conv2's
+    weight gradient is enqueued before conv2's input gradient, BN1's finalize (alone) is the narrow one,
+    conv1's weight gradient comes last, and the main stream waits for the side stream once, after everything.
+    Without the side stream: no waits, no narrow finalize, stem order input gradient -> BN1 finalize -> conv2's
+    weight gradient."""
+    from xcp import _lib
+    from xcp.engine import pc
+    eng, calls, nfwd, log = _xception_step_trace(monkeypatch, True)
+    side = eng._side.name
+    assert side != "main"
+    trace = calls.trace
+    assert (nfwd, len(trace) - nfwd, len(log)) == (244, 465, 49)
+    assert all(st == "main" for st, _, _ in trace[:nfwd])
+    bwd = range(nfwd, len(trace))
+    launches = [i for i in bwd if trace[i][1] not in _lib.SIZE_QUERIES]
+    side_waits = [n for w, o, n in log if (w, o) == (side, "main")]
+    assert [(w, o) for w, o, _ in log].count(("main", side)) == 1 and len(side_waits) == 48
+
+    def behind_main(i):
+        """the side stream waited for the main stream after the main stream's last call before call i"""
+        j = max(k for k in range(i) if trace[k][0] == "main")
+        return any(j < n <= i for n in side_waits)
+
+    # ---- stream placement
+    wg = next(i for i in bwd if trace[i][1] == "xcp_conv3x3_wgrad")
+    dg = next(i for i in bwd if trace[i][1] == "xcp_conv3x3")
+    assert trace[dg][2][0] == 1 and wg < dg   # (mode 1: conv2's input gradient)
+    finish = [i for i in launches if wg < i < dg]
+    assert [trace[i][1] for i in finish] == ["xcp_colreduce_f32", "xcp_permute3"]
+    on_side = {i for i in launches if trace[i][1] in ("xcp_gemm_tn", "xcp_colreduce_multi", "xcp_conv3x3_wgrad")}
+    on_side.update(finish)
+    for i in launches:
+        assert (trace[i][0] == side) == (i in on_side), (i, trace[i])
+        assert trace[i][0] in ("main", side)
+    # ---- the GEMMs and slab reductions, in order: what the model's structure implies
+    fused = {(128, 64), (128, 128), (256, 128), (256, 256)}   # (cout, cin) the fake library gives to xcp_unit_bwd
+
+    def unit(u, M):
+        if (u.cout, u.cin) in fused:
+            return [("main", "xcp_unit_bwd", M, u.cout, u.cin)]
+        return [("main", "xcp_gemm_nt", M, pc(u.cin), pc(u.cout)), (side, "xcp_gemm_tn", M, u.cout, u.cin)]
+
+    H, hs = 33, []   # 71 -> conv1 35 -> conv2 33
+    for b in eng.blocks:
+        hs.append(H)
+        H = (H - 1) // 2 + 1 if b.pool else H
+    want = [e for u in reversed(eng.exit_units) for e in unit(u, 2 * H * H)] + [(side, "xcp_colreduce_multi")]
+    for b, h in zip(reversed(eng.blocks), reversed(hs)):
+        if b.skip is not None:
+            Ms = 2 * ((h - 1) // b.stride + 1) ** 2
+            want += [(side, "xcp_gemm_tn", Ms, b.cout, b.cin), ("main", "xcp_gemm_nt", Ms, pc(b.cin), pc(b.cout))]
+        want += [e for u in reversed(b.units) for e in unit(u, 2 * h * h)] + [(side, "xcp_colreduce_multi")]
+    dims = {"xcp_gemm_nt": lambda a: (a[4], a[5], a[6]), "xcp_gemm_tn": lambda a: (a[3], a[4], a[5]),
+            "xcp_unit_bwd": lambda a: (a[1], a[2], a[3]), "xcp_colreduce_multi": lambda a: ()}
+    got = [(trace[i][0], trace[i][1], *dims[trace[i][1]](trace[i][2])) for i in launches if trace[i][1] in dims]
+    assert got == want
+    assert sum(1 for e in got if e[1] == "xcp_colreduce_multi") == 13
+    assert sum(1 for e in got if e[1] == "xcp_unit_bwd") == 4
+    for i in launches:
+        if trace[i][1] in ("xcp_gemm_tn", "xcp_colreduce_multi", "xcp_conv3x3_wgrad"):
+            assert behind_main(i), (i, trace[i])
+    # ---- stem tail
+    fin = [i for i in bwd if trace[i][1] == "xcp_bn_bwd_finalize_part"]
+    assert [i for i in fin if trace[i][2][-1] & 2] == [fin[-1]] and trace[fin[-1]][2][1] == 32   # BN1 alone is narrow
+    c1 = next(i for i in bwd if trace[i][1] == "xcp_conv1_wgrad_bn")
+    assert dg < fin[-1] < c1
+    assert all(trace[i][1] == "xcp_colreduce_f32" for i in launches if i > c1)   # (only its own slab reduction)
+    assert [n for w, o, n in log if (w, o) == ("main", side)] == [len(trace)]
+    # ---- without the side stream
+    _, calls, nfwd, log = _xception_step_trace(monkeypatch, False)
+    trace = calls.trace
+    assert (nfwd, len(trace) - nfwd, log) == (244, 465, [])
+    assert all(st == "main" for st, _, _ in trace)
+    assert not any(a[-1] & 2 for _, name, a in trace if name == "xcp_bn_bwd_finalize_part")
+    tail = [name for _, name, a in trace[nfwd:] if name in ("xcp_conv3x3", "xcp_conv3x3_wgrad", "xcp_conv1_wgrad_bn")
+            or (name == "xcp_bn_bwd_finalize_part" and a[1] == 32)]
+    assert tail == ["xcp_conv3x3", "xcp_bn_bwd_finalize_part", "xcp_conv3x3_wgrad", "xcp_conv1_wgrad_bn"]
 
 
 def _streams_worker(rank, world, port, out):
@@ -389,7 +508,7 @@ def _streams_worker(rank, world, port, out):
     FILL["v"] = float(rank + 1)
     from xcp import ddp, engine
     engine.WGRAD_SIDE_STREAM = True
-    _install_fake_streams(calls)
+    _install_fake_streams(calls, _MP())
     from Models.Xception import xception
     torch.manual_seed(0)
     m = xception(num_classes=1)

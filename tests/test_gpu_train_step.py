@@ -286,18 +286,19 @@ def test_graph_captured_train_step_matches_eager(gpu):
         assert torch.equal(sa[k], sb[k]), k
 
 
-@pytest.mark.parametrize("flag", ["WGRAD_DEFER", "WGRAD_FIRST", "SKIP_WGRAD_LATE"])
-def test_wgrad_schedule_switches_bitwise(gpu, monkeypatch, flag):
-    """The engine's side-stream schedule switches (a unit's weight gradient launched before its input gradient,
-    after the next unit's, the skip conv's after the block) only reorder independent launches: every gradient
-    of a bf16 xception backward is bit for bit the default schedule's."""
+def test_side_stream_backward_bitwise(gpu, monkeypatch):
+    """The weight-gradient side stream only moves independent launches off the main stream (the tensors it reads
+    are held until the main stream has waited for it, its slab reductions go out after it has waited for the
+    main stream): every gradient of a bf16 xception backward is bit for bit that of the same backward run in
+    order on one stream.  96^2 is the smallest frame that still passes every pooled block and the stride-2
+    skips, down to 3x3 in the exit flow."""
     import xcp
     from xcp import engine
     from Models.Xception import xception
     x = seeded_uniform((4, 3, 96, 96), 37).to(gpu)
     grads = []
-    for on in (False, True):
-        monkeypatch.setattr(engine, flag, on)
+    for on in (True, False):
+        monkeypatch.setattr(engine, "WGRAD_SIDE_STREAM", on)
         torch.manual_seed(0)
         m = xception(num_classes=1).to(gpu).train()
         with xcp.precision("bf16"):
