@@ -708,14 +708,6 @@ constexpr int TH_FWD = 4, TH_DGRAD = 2, MAXIW_FWD = 149, MAXIW_DGRAD = 147;
 // waves per workgroup (two per SIMD); the 64-deep dgrad keeps 144 VGPRs of kernel fragments
 // and has no room for the rotating read pipeline
 constexpr int NW_FWD = 8, NW_DGRAD = 8;
-// XCP_CONV3_FWD_2WG=1: the forward as two workgroups of 4 waves per CU on 2-row tiles (2 x 78 KB of LDS):
-// twice the tiles in flight per CU (A/B)
-constexpr int TH_FWD2 = 2, NW_FWD2 = 4;
-bool conv3_fwd_2wg() {   // (read per call: a test compares both forms in one process)
-  const char* e = getenv("XCP_CONV3_FWD_2WG");
-  return e && e[0] == '1';
-}
-
 
 int conv3_cus() {
   static const int cus = [] {
@@ -747,9 +739,8 @@ extern "C" {
 int xcp_conv3x3_parts(int mode, int N, int IH, int IW) {
   if (IW > (mode == 0 ? MAXIW_FWD : MAXIW_DGRAD)) return 0;
   const int OH = mode == 0 ? IH - 2 : IH + 2;
-  const bool two = mode == 0 && conv3_fwd_2wg();
-  const int th = mode == 0 ? (two ? TH_FWD2 : TH_FWD) : TH_DGRAD;
-  const int tiles = N * ((OH + th - 1) / th), cap = (two ? 2 : 1) * conv3_cus();
+  const int th = mode == 0 ? TH_FWD : TH_DGRAD;
+  const int tiles = N * ((OH + th - 1) / th), cap = conv3_cus();
   return tiles < cap ? tiles : cap;
 }
 
@@ -765,19 +756,15 @@ int xcp_conv3x3(int mode, const void* X, const void* W, void* Y, float* stats, i
   const dim3 grid((unsigned)xcp_conv3x3_parts(mode, N, IH, IW));
   const bf16 *x = (const bf16*)X, *w = (const bf16*)W;
   bf16* y = (bf16*)Y;
-#define XCP_C3F(TH, NW, STATS, ACT)                                                                                  \
-  hipLaunchKernelGGL((conv3x3_kernel<32, 64, 0, TH, MAXIW_FWD, STATS, NW, true, ACT>), grid, dim3(64 * NW), 0, st, x, w, y, \
-                     stats, N, IH, IW, in_scale, in_shift)
+#define XCP_C3F(STATS, ACT)                                                                                          \
+  hipLaunchKernelGGL((conv3x3_kernel<32, 64, 0, TH_FWD, MAXIW_FWD, STATS, NW_FWD, true, ACT>), grid, dim3(64 * NW_FWD), 0, st, \
+                     x, w, y, stats, N, IH, IW, in_scale, in_shift)
   if (mode == 0) {
-    const bool two = conv3_fwd_2wg(), act = in_scale != nullptr;
-    if (two && stats && act) XCP_C3F(TH_FWD2, NW_FWD2, true, true);
-    else if (two && stats) XCP_C3F(TH_FWD2, NW_FWD2, true, false);
-    else if (two && act) XCP_C3F(TH_FWD2, NW_FWD2, false, true);
-    else if (two) XCP_C3F(TH_FWD2, NW_FWD2, false, false);
-    else if (stats && act) XCP_C3F(TH_FWD, NW_FWD, true, true);
-    else if (stats) XCP_C3F(TH_FWD, NW_FWD, true, false);
-    else if (act) XCP_C3F(TH_FWD, NW_FWD, false, true);
-    else XCP_C3F(TH_FWD, NW_FWD, false, false);
+    const bool act = in_scale != nullptr;
+    if (stats && act) XCP_C3F(true, true);
+    else if (stats) XCP_C3F(true, false);
+    else if (act) XCP_C3F(false, true);
+    else XCP_C3F(false, false);
   } else {
     hipLaunchKernelGGL((conv3x3_kernel<64, 32, 2, TH_DGRAD, MAXIW_DGRAD, false, NW_DGRAD, false>), grid, dim3(64 * NW_DGRAD), 0, st,
                        x, w, y, stats, N, IH, IW, nullptr, nullptr);

@@ -35,12 +35,12 @@ struct TileGeo {
   int TH, TW, HP, WP, nth, ntw, nseg;
 };
 
-inline TileGeo tile_geo(int H, int W, int maxpx, int segl = SEGL) {
+inline TileGeo tile_geo(int H, int W, int maxpx) {
   TileGeo g;
   g.ntw = (W + 39) / 40;
   g.TW = (W + g.ntw - 1) / g.ntw;
-  g.nseg = (g.TW + segl - 1) / segl;
-  g.WP = g.nseg * segl + 2;
+  g.nseg = (g.TW + SEGL - 1) / SEGL;
+  g.WP = g.nseg * SEGL + 2;
   int thmax = maxpx / g.WP - 2;
   if (thmax < 1) thmax = 1;
   g.nth = (H + thmax - 1) / thmax;
@@ -263,10 +263,10 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(DwArgs a) {
 }
 
 // The same forward with two channel dwords (4 bf16 channels) per lane: 8 lanes per 64-B pixel
-// slice, 32 row workers of SG-pixel segments, one 8-B store per output pixel and lane (half the
+// slice, 32 row workers of SEGL-pixel segments, one 8-B store per output pixel and lane (half the
 // store instructions of dw_fwd_kernel's 4-B stores); the per-channel fma chain is the same, so
 // the outputs are bitwise those of dw_fwd_kernel.
-template <int ACT, int MAXPX, int SG>
+template <int ACT, int MAXPX>
 __global__ __launch_bounds__(256) void dw_fwd_w2_kernel(DwArgs a) {
   constexpr int FS = SLICE, LANES = FS / 8, NWK = 256 / LANES, CPL = 4;
   __shared__ __attribute__((aligned(16))) char sA[MAXPX * FS];
@@ -299,21 +299,21 @@ __global__ __launch_bounds__(256) void dw_fwd_w2_kernel(DwArgs a) {
   int r = wk / nseg, sg = wk - r * nseg;
   for (int it = wk; it < items; it += NWK) {
     const int oh = th0 + r;
-    const int x0 = sg * SG;
+    const int x0 = sg * SEGL;
     if (oh < a.H) {
       const char* base = lbase + (r * g.WP + x0) * FS;
-      float win[3][SG + 2][CPL];
+      float win[3][SEGL + 2][CPL];
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-        for (int k = 0; k < SG + 2; ++k) {
+        for (int k = 0; k < SEGL + 2; ++k) {
           const uint2 u = *reinterpret_cast<const uint2*>(base + (ky * g.WP + k) * FS);
           unpack(u.x, win[ky][k], (bf16*)nullptr);
           unpack(u.y, win[ky][k] + 2, (bf16*)nullptr);
         }
       const int off = ((oh * a.W + tw0 + x0) * a.C + c) * 2;
 #pragma unroll
-      for (int j = 0; j < SG; ++j) {
+      for (int j = 0; j < SEGL; ++j) {
         float o[CPL];
 #pragma unroll
         for (int e = 0; e < CPL; ++e) {
@@ -338,18 +338,10 @@ __global__ __launch_bounds__(256) void dw_fwd_w2_kernel(DwArgs a) {
   }
 }
 
-// bf16 64-B-slice forwards run dw_fwd_w2_kernel with 5-pixel segments by default: 67 -> 64.5 us
-// at 19^2 x 736, 262 -> 246 at 37^2, 766 -> 733 at 147^2 x 128, bitwise-equal outputs
-// (tools/kbench.py dwshapes fingerprints, profiles/r03_dw_fwd_w2_ab.txt).  XCP_DW_FWD_W2=0 selects
-// dw_fwd_kernel, =4 4-pixel segments (A/B).
-int dw_fwd_w2() {
-  static const int v = [] {
-    const char* e = getenv("XCP_DW_FWD_W2");
-    const int k = e ? atoi(e) : 5;
-    return k == 4 || k == 5 ? k : 0;
-  }();
-  return v;
-}
+// bf16 64-B-slice forwards always run dw_fwd_w2_kernel; dw_fwd_kernel serves fp32 and the 128-B
+// slices.  Against dw_fwd_kernel: 67 -> 64.5 us at 19^2 x 736, 262 -> 246 at 37^2, 766 -> 733 at
+// 147^2 x 128, bitwise-equal outputs; 5-pixel segments beat 4-pixel ones (tools/kbench.py dwshapes
+// fingerprints, profiles/r03_dw_fwd_w2_ab.txt).
 
 // ---------------------------------------------------------------------------------
 // Fused backward.  Per pixel p:
@@ -411,10 +403,10 @@ inline int fwd_slice_bytes(int C, int esz, int H, int W) {
 // Backward: one WAVE owns one channel slice (64 B: 32 bf16 / 16 fp32 channels) of one
 // frame over RCOLS = 20 output columns and walks down all H rows: lane (cl, s) =
 // (lane & 15, lane >> 4) holds one channel dword (2 bf16 -> float2, packed
-// v_pk_fma_f32 math) for the 5 output columns 5s .. 5s+4 of the wave's column range,
-// with rolling 3-row register windows.  dW / BN partial sums are reduced over the 4
-// lane segments with cross-lane shuffles and written once per (frame, column group):
-// P = N * ceil(W / 20).
+// v_pk_fma_f32 math) for the 5 output columns 5s .. 5s+4 of the wave's column range
+// (7-column register windows of the dY rows: one at a time, or three rolling ones, see
+// dw_bwd_lds_kernel).  dW / BN partial sums are reduced over the 4 lane segments with
+// cross-lane shuffles and written once per (frame, column group): P = N * ceil(W / 20).
 constexpr int RS = 5, RNS = 4, RCOLS = RS * RNS;
 typedef float rf2 __attribute__((ext_vector_type(2)));
 
@@ -565,52 +557,52 @@ XCP_DEV void store_row(T* frame, int h, int W, int C, const RowLanes& rl, const 
   }
 }
 
-// LDS reads of the DMA ring by inline asm (XCP_DW_BWD_ASM=1): while the output staging was a second
-// __shared__ object, a plain C++ read of the ring made hipcc drain every outstanding vector-memory
-// operation first (s_waitcnt vmcnt(0)), right after a step had issued the look-ahead rows; the asm
-// reads avoided that.  With one LDS object the plain reads carry no such wait
-// (test_dma_pipelines_not_drained_by_compiler_waits).  The counted vmwait at the top of a step is what
-// orders the ring; ring_fence() retires the asm reads before their values are used (pinned through
-// "+v" operands, so no use is scheduled ahead of the wait).
-XCP_DEV unsigned ring_u32(const char* p) {
-  unsigned v;
-  asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"((unsigned)(size_t)(const __attribute__((address_space(3))) char*)(p))
-               : "memory");
-  return v;
-}
-template <int N>
-XCP_DEV void ring_fence(unsigned (&v)[N]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
-}
-XCP_DEV void ring_fence1(unsigned& v) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  asm volatile("" : "+v"(v));
-}
-
-// Without a residual input (ROLL = false) the three dY rows a step needs (h-1, h, h+1) are read
-// from the LDS ring one row at a time and consumed at once (dgrad and wgrad FMAs of that row), so
-// only one 7-column window is live instead of three rolling ones: 177 -> 140-152 VGPRs, three
-// waves per SIMD instead of two (the dY ring keeps BD + 3 slots: rows h-1 .. h+1 being read, h+2
-// landed, h+3 staged).  With the residual (ROLL = true) the extra ring slots would cost a
-// workgroup per CU (LDS), so the rolling register windows stay: measured 125.2 vs 138.6 us
-// without, 148.1 vs 142.3 us with the residual at 19^2 x 736 (profiles/r03_dwb_ab.txt).
+// One form per (RES, SKIP): whether the call has a residual input (dRes) and a strided-skip gradient
+// (dSkip).  BD = rows of look-ahead per staged tensor; ring rows per wave = X (BD + 1) + dY + dRes
+// (BD + 1, RES); LDS per workgroup = 4 rings + 5 KB of output staging.
+//
+//   form  RES SKIP  walk       BD  ring rows  LDS / workgroup  waves / SIMD (launch bound)
+//   D      0    0   streaming   1      6          39 KB             4
+//   C      0    1   streaming   1      6          39 KB             3
+//   A      1    0   streaming   1      8          50 KB             3   (also BNRES, xcp_dw_bwd_resbn)
+//   B      1    1   rolling     2      9          56 KB             2
+//
+// Streaming: the three dY rows a step needs (h-1, h, h+1) are read from the LDS ring one row at a
+// time and consumed at once (dgrad and wgrad FMAs of that row), so only one 7-column window is live
+// instead of three rolling ones (177 -> 140-152 VGPRs at BD = 2, 138.6 -> 125.2 us at 19^2 x 736,
+// profiles/r03_dwb_ab.txt); its dY ring keeps BD + 3 slots: rows h-1 .. h+1 being read, h+2 landed,
+// h+3 staged.  One row of look-ahead instead of two then fits a wave more per SIMD (D: 108-116
+// VGPRs in bf16): 137.0 -> 119.4 us at 19^2 x 736, 154.2 -> 144.0 with the residual, 426 -> 398 at 37^2,
+// 113 -> 96 at 10^2 x 1536 (tools/dw_ab.py, profiles/r03_dw_occ4_ab.txt).  The strided-skip calls
+// (C: the first unit of blocks 2, 3 and 12) spill at four waves per SIMD with the skip terms and
+// run at three: -1 ... -2 % against two rows of look-ahead (profiles/r05_dw_skip4_ab.txt).  D
+// re-reads the raw centre values from LDS where the BN sums use them, to fit four waves' registers.
+// B (residual and strided skip: the public op only, no engine call) keeps the rolling register
+// windows and two rows of look-ahead: with the residual, streaming at BD = 2 lost to them (148.1 vs
+// 142.3 us at 19^2 x 736, the extra ring slots cost a workgroup per CU of LDS:
+// profiles/r03_dwb_ab.txt), and the one-row A/Bs above cover no call with both inputs.
 // BNRES: the BN partial sums are taken over the final dX against a.Yb (xcp_dw_bwd_resbn; a template
 // argument so the other forms carry no conditional loads -- a load behind a runtime branch made hipcc
-// drain vmcnt(0) at the branch's join on every row step)
-template <typename T, int ACT, bool RES, bool ROLL, int BDV = 2, int MINW = (ROLL ? 2 : 3), bool SKIP = true,
-          bool BNRES = false, bool ASMRD = false>
-__global__ __launch_bounds__(256, MINW) void dw_bwd_lds_kernel(DwBwdArgs a) {
+// drain vmcnt(0) at the branch's join on every row step).  Only with RES && !SKIP.
+constexpr int dw_bwd_minw(bool res, bool skip) {   // waves per SIMD the launch bound asks for
+  return res && skip ? 2 : (res || skip ? 3 : 4);
+}
+template <typename T, int ACT, bool RES, bool SKIP, bool BNRES>
+__global__ __launch_bounds__(256, (dw_bwd_minw(RES, SKIP))) void dw_bwd_lds_kernel(DwBwdArgs a) {
+  static_assert(!BNRES || (RES && !SKIP), "BNRES: residual input, no strided-skip gradient");
   typedef RV<T> R;
   typedef typename R::V V;
   constexpr int EPT = R::EPT, CPG = 16 * EPT;
-  constexpr int BD = BDV;                                // rows of look-ahead per staged tensor
+  constexpr bool ROLL = RES && SKIP;                     // rolling register windows (form B)
+  constexpr int BD = ROLL ? 2 : 1;                       // rows of look-ahead per staged tensor
+  constexpr int MINW = dw_bwd_minw(RES, SKIP);
   constexpr int NS = BD + 1;                             // X / dRes ring slots
   constexpr int NSG = ROLL ? NS : BD + 3;                // dY ring slots
-  // one LDS object for the rings and the output staging: with a second object the LDS accesses carry
-  // alias scopes, and hipcc then drains every in-flight LDS-DMA (vmcnt(0)) ahead of the first plain
-  // ring read of a step, right after the look-ahead row was issued
+  // one LDS object for the rings and the output staging, read with plain C++ reads: with a second
+  // object the LDS accesses carry alias scopes, and hipcc then drains every in-flight LDS-DMA
+  // (vmcnt(0)) ahead of the first ring read of a step, right after the look-ahead row was issued
+  // (test_dma_pipelines_not_drained_by_compiler_waits; inline-asm ring reads once hid that drain and
+  // lost to this: profiles/r05_dw_bwd_onelds_ab.txt)
   constexpr int RING = (NS + NSG + (RES ? NS : 0)) * LROW;
   __shared__ __attribute__((aligned(16))) char sm[4 * RING + 4 * RCOLS * SLICE];
   const int ncg = (a.W + RCOLS - 1) / RCOLS;
@@ -667,20 +659,11 @@ __global__ __launch_bounds__(256, MINW) void dw_bwd_lds_kernel(DwBwdArgs a) {
   const T* dSkip = reinterpret_cast<const T*>(a.dSkip);
   T* dX = reinterpret_cast<T*>(a.dX) + fbase;
   const int lofs = sg * RS * SLICE + cl * 4;
-  // ring reads: inline asm retired by fence() (ASMRD), or plain C++ reads (hipcc's own waits; see
-  // ring_u32 above and launch_bwd_act for where each form is used)
-  auto rd = [&](const char* row, int k) {
-    if constexpr (ASMRD) return ring_u32(row + lofs + k * SLICE);
-    else return *reinterpret_cast<const unsigned*>(row + lofs + k * SLICE);
-  };
-  auto fence = [&](auto& v) {
-    if constexpr (ASMRD) ring_fence(v);
-  };
+  auto rd = [&](const char* row, int k) { return *reinterpret_cast<const unsigned*>(row + lofs + k * SLICE); };
   auto cvtg = [&](const char* row, V (&gy)[RS + 2]) {
     unsigned u[RS + 2];
 #pragma unroll
     for (int k = 0; k < RS + 2; ++k) u[k] = rd(row, k);
-    fence(u);
 #pragma unroll
     for (int k = 0; k < RS + 2; ++k) gy[k] = R::unpack(u[k]);   // staged zero padding
   };
@@ -733,7 +716,6 @@ __global__ __launch_bounds__(256, MINW) void dw_bwd_lds_kernel(DwBwdArgs a) {
     unsigned xu[RS + 2];
 #pragma unroll
     for (int k = 0; k < RS + 2; ++k) xu[k] = rd(sxh, k);
-    fence(xu);
 #pragma unroll
     for (int k = 0; k < RS + 2; ++k) {
       const unsigned u = xu[k];
@@ -753,7 +735,6 @@ __global__ __launch_bounds__(256, MINW) void dw_bwd_lds_kernel(DwBwdArgs a) {
     if constexpr (RES) {
 #pragma unroll
       for (int j = 0; j < RS; ++j) pres[j] = rd(srh, j + 1);
-      fence(pres);
     }
     stage_row<T>(X, h + BD, hx, a.W, a.C, rl_ld, sx(h + BD), lane);          // slot of X row h-1
     stage_row<T>(G, h + 1 + BD, hg, a.W, a.C, rl_ld, sgs(h + 1 + BD), lane);   // slot of dY row h
@@ -817,12 +798,8 @@ __global__ __launch_bounds__(256, MINW) void dw_bwd_lds_kernel(DwBwdArgs a) {
         const V dz = valid ? R::unpack(R::pack(s)) : V(0.f);   // the stored (rounded) dz
         bs1 += dz;
         unsigned xraw;
-        if constexpr (KEEP_XR) {
-          xraw = xr[j];
-        } else {
-          xraw = rd(sxh, j + 1);
-          if constexpr (ASMRD) ring_fence1(xraw);
-        }
+        if constexpr (KEEP_XR) xraw = xr[j];
+        else xraw = rd(sxh, j + 1);
         bs2 = vfma(dz, (R::unpack(xraw) - mu) * is, bs2);
       }
       if constexpr (RES) s += R::unpack(pres[j]);
@@ -900,28 +877,6 @@ __global__ __launch_bounds__(256, MINW) void dw_bwd_lds_kernel(DwBwdArgs a) {
   }
 }
 
-// XCP_DW_BWD_ROLL=1: the rolling-window form for every variant (the round-2 kernel; A/B)
-bool dw_bwd_roll_all() {
-  static const bool v = [] {
-    const char* e = getenv("XCP_DW_BWD_ROLL");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-// Default for calls without a strided-skip input: the streaming form with one row of look-ahead
-// (6 ring rows per wave, 39 KB per workgroup, 112-122 VGPRs: four waves per SIMD; with a residual
-// 8 rows, 50 KB, three).  Against the BD = 2 forms at the step's shapes (tools/dw_ab.py,
-// profiles/r03_dw_occ4_ab.txt): 137.0 -> 119.4 us at 19^2 x 736, 154.2 -> 144.0 with the residual,
-// 426 -> 398 at 37^2, 113 -> 96 at 10^2 x 1536; outputs bitwise equal except the residual form's dX
-// (bf16 rounding of the reordered window sum).  XCP_DW_BWD_OCC4=0 keeps the BD = 2 forms (A/B).
-bool dw_bwd_occ4() {
-  static const bool v = [] {
-    const char* e = getenv("XCP_DW_BWD_OCC4");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
 // Row bands per frame: the row walk of a frame split into b bands of ceil(H / b) rows (one wave
 // each; a band re-reads the dY rows just above and below it).  Default: 3 bands for frames of 64
 // rows or more (147^2 x 128: 1,101 -> 1,041 us; 74^2 x 256: 560 -> 548), one below (at 19^2 two
@@ -943,46 +898,16 @@ int dw_bwd_xcd() {
   return e && e[0] == '0' ? 0 : 1;
 }
 
-// Ring reads: plain C++ reads by default.  Round 4 measured inline-asm reads faster below 32 rows
-// (118.4 -> 111.0 us at 19^2 x 736, profiles/r04_dw_asm_ab.txt) because hipcc drained vmcnt(0) ahead
-// of the first plain ring read of every step; with the rings and the staging in one LDS object (round
-// 5) that drain is gone and the plain form (offsets folded into the reads, no per-window fences) is as
-// fast or faster at every step shape (19^2: 103.6 / 102.6 us plain / asm, 10^2: 90.9 / 96.7;
-// profiles/r05_dw_bwd_onelds_ab.txt).  XCP_DW_BWD_ASM=1 forces the asm form (read per call).
-bool dw_bwd_asm_reads(int) {
-  const char* e = getenv("XCP_DW_BWD_ASM");
-  return e && e[0] == '1';
-}
-
-// XCP_DW_BWD_SKIP4=0: calls with a strided-skip gradient (the first unit of blocks 2, 3 and 12) keep the
-// two-rows-of-look-ahead form instead of the one-row form with plain ring reads (A/B; read per call)
-bool dw_bwd_skip4() {
-  const char* e = getenv("XCP_DW_BWD_SKIP4");
-  return !(e && e[0] == '0');
-}
-
 template <typename T, int ACT>
 void launch_bwd_act(const DwBwdArgs& a, int blocks, hipStream_t st) {
-  // every form reads the ring with plain C++ reads unless XCP_DW_BWD_ASM=1 (the inline-asm form, kept
-  // for the bitwise A/B test_dw_bwd_ring_read_forms)
-  const bool asmrd = dw_bwd_asm_reads(a.H);
-#define DWB(...)                                                                                  \
-  do {                                                                                            \
-    if (asmrd) hipLaunchKernelGGL((dw_bwd_lds_kernel<__VA_ARGS__, true>), dim3(blocks), dim3(256), 0, st, a); \
-    else hipLaunchKernelGGL((dw_bwd_lds_kernel<__VA_ARGS__, false>), dim3(blocks), dim3(256), 0, st, a);     \
-  } while (0)
-  if (a.dRes && dw_bwd_occ4() && !a.dSkip) {
-    if (a.Yb) DWB(T, ACT, true, false, 1, 3, false, true);
-    else DWB(T, ACT, true, false, 1, 3, false, false);
-  } else if (a.dRes && a.Yb)
-    DWB(T, ACT, true, true, 2, 2, true, true);
-  else if (a.dRes) DWB(T, ACT, true, true, 2, 2, true, false);
-  else if (dw_bwd_roll_all()) DWB(T, ACT, false, true, 2, 2, true, false);
-  else if (dw_bwd_occ4() && a.dSkip && dw_bwd_skip4())
-    DWB(T, ACT, false, false, 1, 3, true, false);
-  else if (dw_bwd_occ4() && !a.dSkip)
-    DWB(T, ACT, false, false, 1, 4, false, false);
-  else DWB(T, ACT, false, false, 2, 3, true, false);
+  // (dw_bwd_impl refuses a.Yb without a.dRes or with a.dSkip)
+#define DWB(RES, SKIP, BNRES) \
+  hipLaunchKernelGGL((dw_bwd_lds_kernel<T, ACT, RES, SKIP, BNRES>), dim3(blocks), dim3(256), 0, st, a)
+  if (a.dRes && a.dSkip) DWB(true, true, false);
+  else if (a.dRes && a.Yb) DWB(true, false, true);
+  else if (a.dRes) DWB(true, false, false);
+  else if (a.dSkip) DWB(false, true, false);
+  else DWB(false, false, false);
 #undef DWB
 }
 
@@ -1020,19 +945,13 @@ int xcp_dw_fwd(int dtype, int act, const void* X, void* Y, const float* Wt, cons
     return launch_fwd<float, FWD_MAXPX128, 128>(act, a, stream);
   }
   DwArgs a{X, Y, Wt, scale, shift, N, H, W, C, ngroups_for(C, dtype), tile_geo(H, W, FWD_MAXPX)};
-  if (dtype == XCP_BF16 && dw_fwd_w2()) {
-    const int sg = dw_fwd_w2();
-    a.g = tile_geo(H, W, FWD_MAXPX, sg);
+  if (dtype == XCP_BF16) {
     const int blocks = a.N * a.g.nth * a.g.ntw * a.ngroups;
-#define XCP_W2(SGV)                                                                                                  \
-    if (act == ACT_NONE) hipLaunchKernelGGL((dw_fwd_w2_kernel<ACT_NONE, FWD_MAXPX, SGV>), dim3(blocks), dim3(256), 0, stream, a); \
-    else if (act == ACT_RELU) hipLaunchKernelGGL((dw_fwd_w2_kernel<ACT_RELU, FWD_MAXPX, SGV>), dim3(blocks), dim3(256), 0, stream, a); \
-    else hipLaunchKernelGGL((dw_fwd_w2_kernel<ACT_BNRELU, FWD_MAXPX, SGV>), dim3(blocks), dim3(256), 0, stream, a);
-    if (sg == 4) { XCP_W2(4) } else { XCP_W2(5) }
-#undef XCP_W2
+    if (act == ACT_NONE) hipLaunchKernelGGL((dw_fwd_w2_kernel<ACT_NONE, FWD_MAXPX>), dim3(blocks), dim3(256), 0, stream, a);
+    else if (act == ACT_RELU) hipLaunchKernelGGL((dw_fwd_w2_kernel<ACT_RELU, FWD_MAXPX>), dim3(blocks), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((dw_fwd_w2_kernel<ACT_BNRELU, FWD_MAXPX>), dim3(blocks), dim3(256), 0, stream, a);
     return (int)hipGetLastError();
   }
-  if (dtype == XCP_BF16) return launch_fwd<bf16, FWD_MAXPX, 64>(act, a, stream);
   return launch_fwd<float, FWD_MAXPX, 64>(act, a, stream);
 }
 

@@ -391,36 +391,6 @@ def test_dw_bwd_row_bands(ops, gpu, monkeypatch, bands, N, C, H, act, res, skip)
         assert torch.equal(outs[2][2], outs[1][2])
 
 
-@pytest.mark.parametrize("N,C,H,act,res", [(64, 736, 19, 2, False), (16, 256, 37, 2, False), (4, 128, 74, 1, False),
-                                           (32, 1536, 10, 0, False), (64, 736, 19, 1, True)])
-def test_dw_bwd_ring_read_forms(ops, gpu, monkeypatch, N, C, H, act, res):
-    """Ring reads by inline asm (XCP_DW_BWD_ASM=1) or plain C++ reads (the default): the same
-    arithmetic on the same values, every output bitwise equal."""
-    W = H
-    g = torch.Generator(device=gpu).manual_seed(3 * N + C + H)
-    dt = torch.bfloat16
-    x = torch.randn(N * H * W, C, device=gpu, generator=g).to(dt)
-    dy = torch.randn(N * H * W, C, device=gpu, generator=g).to(dt)
-    Wt = torch.randn(9, C, device=gpu, generator=g) / 3
-    sc = torch.rand(C, device=gpu, generator=g) + 0.5
-    sh = torch.randn(C, device=gpu, generator=g) * 0.2
-    dR = torch.randn(N * H * W, C, device=gpu, generator=g).to(dt) if res else None
-    st = {"mean": torch.randn(C, device=gpu, generator=g) * 0.1,
-          "invstd": torch.rand(C, device=gpu, generator=g) + 0.5} if act == 2 else None
-    outs = []
-    for form in ("0", "1"):
-        monkeypatch.setenv("XCP_DW_BWD_ASM", form)
-        dX = torch.full((N * H * W, C), float("nan"), device=gpu, dtype=dt)
-        dW = torch.empty(C * 9, device=gpu)
-        bnpart, P = ops.dw_bwd(act, dy, x, Wt, sc, sh, dX, dW, N, H, W, C, dRes=dR, bn_stats=st)
-        torch.cuda.synchronize()
-        outs.append((dX, dW, bnpart.clone() if bnpart is not None else None))
-    assert not torch.isnan(outs[1][0].float()).any()
-    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    if act == 2:
-        assert torch.equal(outs[0][2], outs[1][2])
-
-
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("N", [2, 701])
 def test_dw_bwd_residual_and_skip(ops, gpu, dt, N):
@@ -1068,28 +1038,6 @@ def test_conv3x3_bn_relu_on_load_bitwise(ops, gpu, N, IH, IW):
     ref_dw = torch.nn.grad.conv2d_weight(nchw(a.view(N, IH, IW, 32)).float(), (64, 32, 3, 3),
                                          nchw(dy.view(N, OH, OW, 64)).float())
     assert rel_err(dws[1].view(64, 3, 3, 32).permute(0, 3, 1, 2), ref_dw) < 1e-4
-
-
-@pytest.mark.parametrize("N,IH,IW", [(3, 149, 149), (2, 9, 40)])
-def test_conv3x3_fwd_two_workgroup_form(ops, gpu, monkeypatch, N, IH, IW):
-    """XCP_CONV3_FWD_2WG=1 (two 4-wave workgroups per CU on 2-row tiles): the same MFMAs per output
-    item, so the output is bitwise the one-workgroup form's; the BN partial rows (one per workgroup)
-    sum to the same statistics."""
-    g = torch.Generator(device=gpu).manual_seed(IH + N)
-    x = torch.randn(N * IH * IW, 32, device=gpu, generator=g).bfloat16()
-    Wp = (torch.randn(64, 288, device=gpu, generator=g) / 17).bfloat16()
-    OH, OW = IH - 2, IW - 2
-    outs = []
-    for v in ("0", "1"):
-        monkeypatch.setenv("XCP_CONV3_FWD_2WG", v)
-        R = ops.conv3x3_parts(0, N, IH, IW)
-        stats = torch.full((R, 2, 64), float("nan"), device=gpu)
-        Y = torch.full((N * OH * OW, 64), float("nan"), device=gpu, dtype=torch.bfloat16)
-        ops.conv3x3(0, x, Wp, Y, stats, N, IH, IW)
-        torch.cuda.synchronize()
-        outs.append((Y, stats.double().sum(0)))
-    assert torch.equal(outs[0][0], outs[1][0])
-    torch.testing.assert_close(outs[1][1], outs[0][1], rtol=1e-6, atol=1e-3)
 
 
 @pytest.mark.parametrize("max_norm", [None, 1.0, 1e-3])

@@ -1,8 +1,8 @@
 """A/B of the depthwise backward against the committed version (git HEAD's csrc/dwconv.hip, built
 into probe/libdw_base.so, a path the GPU upload carries -- delete it afterwards): both libraries'
 xcp_dw_bwd on identical inputs at the step's shapes (with and without a strided-skip gradient),
-interleaved rounds, median launch time; the new library also with XCP_DW_BWD_SKIP4=0; outputs compared
-against the base (max |diff| of dX, dW partials, BN sums).
+interleaved rounds, median launch time; outputs compared against the base (max |diff| of dX, dW
+partials, BN sums).
 
   python tools/dw_ab.py build [rev]   # here (rev: git revision of the baseline, default HEAD)
   python tools/dw_ab.py run           # GPU box
@@ -53,7 +53,7 @@ def run():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     st = torch.cuda.current_stream().cuda_stream
-    variants = {"base": (libs["base"], None), "new": (libs["new"], None), "skip4off": (libs["new"], "S0")}
+    variants = {"base": libs["base"], "new": libs["new"]}
     # (N, H, W, C, act, residual, strided-skip gradient): the skip shapes are the first units of blocks 2, 3, 12
     shapes = [(256, 19, 19, 736, 2, False, False), (256, 19, 19, 736, 1, True, False), (256, 37, 37, 736, 2, False, False),
               (256, 74, 74, 256, 2, False, False), (256, 147, 147, 128, 2, False, False), (256, 10, 10, 1536, 2, False, False),
@@ -78,16 +78,9 @@ def run():
 
         def call(k):
             dX, dWp, bnp = outs[k]
-            lib, env = variants[k]
-            os.environ.pop("XCP_DW_BWD_ASM", None)
-            os.environ.pop("XCP_DW_BWD_SKIP4", None)
-            if env == "S0":
-                os.environ["XCP_DW_BWD_SKIP4"] = "0"
-            elif env is not None:
-                os.environ["XCP_DW_BWD_ASM"] = env
-            rc = lib.xcp_dw_bwd(1, act, p(dY), p(X), p(Wt), p(sc), p(sh), p(dR), p(dS), sO if skip else 0,
-                                sO if skip else 0, 2 if skip else 1, 0, p(dX), p(dWp),
-                                    p(bnp), p(mu) if act == 2 else None, p(isd) if act == 2 else None, N, H, W, C, st)
+            rc = variants[k].xcp_dw_bwd(1, act, p(dY), p(X), p(Wt), p(sc), p(sh), p(dR), p(dS), sO if skip else 0,
+                                        sO if skip else 0, 2 if skip else 1, 0, p(dX), p(dWp), p(bnp),
+                                        p(mu) if act == 2 else None, p(isd) if act == 2 else None, N, H, W, C, st)
             assert rc == 0, rc
 
         times = {k: [] for k in variants}
