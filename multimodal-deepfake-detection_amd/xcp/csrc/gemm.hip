@@ -21,7 +21,6 @@
 // LDS rows are 128 B (one 64-deep bf16 / 32-deep fp32 K-stage), 16-B chunks
 // XOR-swizzled with (row>>1)&7 so a 16-lane ds_read_b128 group is conflict-free.
 #include "common.h"
-#include <stdlib.h>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -107,7 +106,6 @@ struct NTArgs {
   float* stats;           // [gridM][2][N] partial (sum, sumsq) or nullptr
   Gather ga;
   int tqs;                // gemm_nt256p_kernel: tile-queue slot + 1 (0: static tile walk)
-  int khalf;              // gemm_nt256p_kernel: a last K-tile with K % 64 in (0, 32] multiplies its first half only
 };
 
 // ---------------------------------------------------------------------------------
@@ -730,8 +728,10 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
 
   f32x4 acc[8][4];
   const int nk = (a.K + 63) / 64;
-  // (XCP_NT_KHALF=0: every K-tile whole; the A/B switch, read per launch on the host)
-  const bool khalf = a.khalf && (a.K & 63) != 0 && (a.K & 63) <= 32;
+  // the last K-tile multiplies only its first 32-deep half when the rest of it is past K (the 728-channel flow
+  // at its 736 pitch: K = 728 / 736, 24 / 32 of the last 64): 32 of the tile's 768 MFMAs per wave skipped, C
+  // and the statistics bitwise equal to the whole K-tile's (profiles/r06_nt_khalf_ab.txt)
+  const bool khalf = (a.K & 63) != 0 && (a.K & 63) <= 32;
   const int fr = lane & 15, fg = lane >> 4;
   bf16x8 af[4][2], bl[2][2], br[2][2];
   // NKS: 32-deep halves of the K-tile to multiply (1: the last K-tile of a K with K % 64 in (0, 32], whose
@@ -854,301 +854,6 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(NTArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
-// Persistent 256x256 NT kernel, two MFMA phases per 64-deep K-tile and the fill issued ~1.5
-// K-tiles ahead (gemm_nt256q_kernel, the default; XCP_NT_LOOP=4 keeps gemm_nt256p_kernel).
-//
-// The four-phase loop above pays 8 s_barrier per K-tile around 16-MFMA phases and issues the
-// next K-tile's fill during the current one (its probe, profiles/r04_nt_probe.txt: MFMAs plus
-// that barrier skeleton 1.31 us per K-tile against 0.86 us of MFMA issue at 2.4 GHz, the fill
-// another 0.47 us exposed).  Here each wave's K-tile is
-//   R0  reads B (its 64 columns) and A-top (its group's first 64 rows): 16 ds_read_b128
-//   M0  32 MFMAs into acc[0..3][0..3]
-//   R1  reads A-bot: 8 ds_read_b128
-//   M1  32 MFMAs into acc[4..7][0..3]
-// with one barrier between consecutive intervals (4 per K-tile) and wave group 1 (waves 4-7)
-// one interval behind group 0, so every interval pairs one group's MFMAs with the other group's
-// LDS reads and DMA issue on each SIMD.  A read interval ends with lgkmcnt(0), so the MFMA
-// interval after it starts on registers that have landed.
-// Ring: the two 64 KB slots of gemm_nt256p_kernel, refilled by region as soon as both groups have
-// read it: a slot's A-top + B region (6 LDS-DMA instructions per wave) is free after both groups'
-// R0, its A-bot region (2 per wave) after both groups' R1.  So during K-tile k a wave issues
-//   R0(k): A-bot of K-tile k+1        R1(k): A-top + B of K-tile k+2
-// which leaves every region 6 intervals (1.5 K-tiles) between its issue and its first reader.
-// K-tiles run on across tiles (the next tile's first two K-tiles are issued during this tile's
-// last two) and a finished tile's epilogue is split over the next tile's read intervals: rows
-// 0-63 of each group (acc[0..3]) are stored and zeroed in R0, rows 64-127 (acc[4..7]) and the BN
-// statistics row in R1 -- beside the other group's MFMAs.
-// Every wave waits for its own fill with one counted vmcnt per region: the count is the number of
-// VMEM instructions the wave issued after the awaited region (epilogue stores are always issued,
-// masked lanes by an out-of-range offset), so each wait retires exactly that region; wave 0's
-// tile-queue fetch can only add a younger instruction (a stricter wait).  Needs K > 64.
-template <bool STATS, int H>
-XCP_DEV void epilogue256_half(f32x4 (&acc)[8][4], const NTArgs& a, __amdgpu_buffer_rsrc_t rC,
-                              __amdgpu_buffer_rsrc_t rS, int m0, int n0, int wr, int wc, int fr, int fg,
-                              float (&red)[2]) {
-  const int bm = m0 / 256, stat_rows = (a.M + 127) / 128;
-  const int mrow = m0 + wr * 128 + fr;
-  const int ncol = n0 + wc * 64;
-  const bool odd = fg & 1;
-  float s1[16], s2[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) s1[q] = s2[q] = 0.f;
-  const int c0 = ncol + (odd ? 16 + (fg - 1) * 4 : fg * 4);
-  static_for<4 * H, 4 * H + 4>([&](auto i) {
-    const int m = mrow + i * 16;
-    const bool mok = m < a.M;
-    uint2 pc[4];
-    static_for<0, 4>([&](auto j) {
-      pc[j] = make_uint2(pk_bf16(acc[i][j][0], acc[i][j][1]), pk_bf16(acc[i][j][2], acc[i][j][3]));
-      const bf16x4 q = __builtin_bit_cast(bf16x4, pc[j]);
-      if constexpr (STATS) {   // (branch-free: rows past M add zero)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float f = mok ? (float)q[r] : 0.f;
-          s1[j * 4 + r] += f;
-          s2[j * 4 + r] = fmaf(f, f, s2[j * 4 + r]);
-        }
-      }
-      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    });
-    const uint2 snd0 = odd ? pc[0] : pc[1], snd1 = odd ? pc[2] : pc[3];
-    uint2 rc0, rc1;
-    rc0.x = __shfl_xor(snd0.x, 16, 64);
-    rc0.y = __shfl_xor(snd0.y, 16, 64);
-    rc1.x = __shfl_xor(snd1.x, 16, 64);
-    rc1.y = __shfl_xor(snd1.y, 16, 64);
-    const uint4 st0 = odd ? make_uint4(rc0.x, rc0.y, pc[1].x, pc[1].y) : make_uint4(pc[0].x, pc[0].y, rc0.x, rc0.y);
-    const uint4 st1 = odd ? make_uint4(rc1.x, rc1.y, pc[3].x, pc[3].y) : make_uint4(pc[2].x, pc[2].y, rc1.x, rc1.y);
-    const unsigned rowb = (unsigned)((long)m * a.ldc * 2);
-    const unsigned o0 = (mok && c0 < a.N) ? rowb + (unsigned)c0 * 2 : BUF_OOB;
-    const unsigned o1 = (mok && c0 + 32 < a.N) ? rowb + (unsigned)(c0 + 32) * 2 : BUF_OOB;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st0), rC, (int)o0, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, st1), rC, (int)o1, 0, 0);
-  });
-  if constexpr (STATS) {   // this half's column sums, reduced over the wave as epilogue256_buf does
-    float u[16], v8[8], v4[4];
-    const bool b3 = fr & 8, b2 = fr & 4, b1 = fr & 2, b0 = fr & 1;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) u[q] = (b3 ? s2[q] : s1[q]) + __shfl_xor(b3 ? s1[q] : s2[q], 8, 64);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v8[q] = (b2 ? u[8 + q] : u[q]) + __shfl_xor(b2 ? u[q] : u[8 + q], 4, 64);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v4[q] = (b1 ? v8[4 + q] : v8[q]) + __shfl_xor(b1 ? v8[q] : v8[4 + q], 2, 64);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) red[q] += (b0 ? v4[2 + q] : v4[q]) + __shfl_xor(b0 ? v4[q] : v4[2 + q], 1, 64);
-    if constexpr (H == 1) {
-      const int col = ncol + ((fr & 7) >> 1) * 16 + fg * 4 + (fr & 1) * 2;
-      const int srow = bm * 2 + wr;
-      const unsigned so = (srow < stat_rows && col < a.N)
-                              ? (unsigned)((((long)srow * 2 + (fr >> 3)) * a.N + col) * 4) : BUF_OOB;
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, make_float2(red[0], red[1])), rS, (int)so, 0, 0);
-      red[0] = red[1] = 0.f;
-    }
-  }
-}
-
-// s_waitcnt vmcnt(n) for the counts gemm_nt256q_kernel forms (steady state 8 first; any other
-// value waits for everything, which is only ever stricter)
-XCP_DEV void vm_wait_q(int n) {
-#define XCP_VMQ(k) if (n == k) { asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); return; }
-  XCP_VMQ(8) XCP_VMQ(16) XCP_VMQ(17) XCP_VMQ(18) XCP_VMQ(19) XCP_VMQ(24) XCP_VMQ(25) XCP_VMQ(2)
-#undef XCP_VMQ
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-XCP_DEV void nt_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-template <bool STATS>
-__global__ __launch_bounds__(512) void gemm_nt256q_kernel(NTArgs a) {
-  constexpr int EA = 8, EB = 8 + (STATS ? 1 : 0);   // epilogue stores per wave in R0 / in R1
-  __shared__ __attribute__((aligned(16))) char smem[2 * K_SLOT + 16];
-  int* const s_next = reinterpret_cast<int*>(smem + 2 * K_SLOT);
-  int* const tq = a.tqs > 0 ? g_nt_tq + (a.tqs - 1) : nullptr;
-  const int gridN = (a.N + 255) / 256, gridM = (a.M + 255) / 256;
-  const int tiles = gridM * gridN, nwg = gridDim.x;
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 2, wc = w & 3;
-  const int arow = (w < 4 ? 16 * w : 128 + 16 * (w - 4));
-  const int brow = 64 * (w >> 1) + 16 * (w & 1);
-  const int lr = lane >> 3;
-  // per lane: the rows it fills of each half-tile (wave base + i * 8 + lr) and the 16-B chunk of the
-  // 128-B row (XOR-swizzled by (row >> 1) & 7 = (i * 4 + lr / 2) & 7: every base is a multiple of 16);
-  // the tile only adds a scalar row offset, so the per-lane part of each offset is tile-independent
-  const int kc8[2] = {((lane & 7) ^ ((lr >> 1) & 7)) * 8, ((lane & 7) ^ ((4 + (lr >> 1)) & 7)) * 8};
-  auto hbase = [&](int h) {   // wave-uniform first row of half-tile h this wave fills
-    return (h == 0 || h == 3) ? arow + (h == 3 ? 64 : 0) : brow + (h == 2 ? 32 : 0);
-  };
-  unsigned lpart[4][2];
-#pragma unroll
-  for (int h = 0; h < 4; ++h)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const bool isA = (h == 0 || h == 3);
-      lpart[h][i] = (unsigned)(((long)(hbase(h) + i * 8 + lr) * (isA ? a.lda : a.ldb) + kc8[i]) * 2);
-    }
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.A), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.B), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(a.C, (short)0, BUF_RECORDS, BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(STATS ? (void*)a.stats : a.C, (short)0,
-                                                                       BUF_RECORDS, BUF_DWORD3);
-  // half-tile h of K-tile kt of tile tt into ring slot sl: 2 instructions
-  auto issue = [&](int tt, int h, int kt, int sl) {
-    const bool isA = (h == 0 || h == 3);
-    const int row0 = hbase(h);
-    const int tb = isA ? (tt / gridN) * 256 : (tt % gridN) * 256;   // (uniform)
-    const unsigned tofs = (unsigned)((long)tb * (isA ? a.lda : a.ldb) * 2);
-    char* d = smem + sl * K_SLOT + (isA ? 0 : K_OP) + row0 * 128;
-    const int kb = kt * 64;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const bool ok = tb + row0 + i * 8 + lr < (isA ? a.M : a.N) && kb + kc8[i] < a.K;
-      const unsigned o = ok ? lpart[h][i] + tofs + kb * 2 : BUF_OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(isA ? rA : rB, (__attribute__((address_space(3))) void*)(d + i * 1024),
-                                               16, o, 0, 0, 0);
-    }
-  };
-  auto issue_atb = [&](int tt, int kt, int sl) {   // 6 instructions
-    issue(tt, 0, kt, sl);
-    issue(tt, 1, kt, sl);
-    issue(tt, 2, kt, sl);
-  };
-
-  int t = xcd_remap(blockIdx.x, nwg);
-  if (t >= tiles) return;
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float red[2] = {0.f, 0.f};
-  const int nk = (a.K + 63) / 64;
-  const int fr = lane & 15, fg = lane >> 4;
-  bf16x8 af[4][2], bf[4][2];
-  // the next tile: known now on the static walk; with the tile queue fetched at each tile's start
-  // and published at K-tile nk-2
-  int tn = t + nwg;
-  bool more = !tq && tn < tiles;
-  // prologue: A-top + B of K-tiles 0 and 1, A-bot of 0; wait for K-tile 0's A-top + B
-  issue_atb(t, 0, 0);
-  issue(t, 3, 0, 0);
-  issue_atb(t, 1, 1);
-  vm_wait_q(8);
-  nt_barrier();
-  if (wr == 1) nt_barrier();
-
-  int sb = 0;              // ring slot of this tile's K-tile 0
-  int pt = 0;              // the finished tile whose epilogue runs during K-tile 0 (when follow)
-  bool follow = false;     // this tile follows another one of this workgroup
-  unsigned nxt = 0;
-  int kt = 0;
-  while (true) {
-    const int sl = (sb + kt) & 1;
-    const char* sa = smem + sl * K_SLOT;
-    const char* sbp = sa + K_OP;
-    const bool last = kt + 1 == nk;
-    const bool e0 = follow && kt == 0;           // epilogue halves in this K-tile's R0 / R1
-    const bool e_prev = follow && kt == 1;       // ... in the previous K-tile's
-    const bool ex1 = !last || more;              // K-tile k+1 exists (this tile's or the next one's)
-    // ---- R0: epilogue rows 0-63, B + A-top fragments, A-bot fill of K-tile k+1
-    if (e0) epilogue256_half<STATS, 0>(acc, a, rC, rS, (pt / gridN) * 256, (pt % gridN) * 256, wr, wc, fr, fg, red);
-    if (kt == 0 && tq && tid == 0)
-      asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(nxt) : "v"(tq), "v"(1u) : "memory");
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        bf[j][ks] = *reinterpret_cast<const bf16x8*>(sbp + swz(wc * 64 + j * 16 + fr, ks * 4 + fg));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        af[i][ks] = *reinterpret_cast<const bf16x8*>(sa + swz(wr * 128 + i * 16 + fr, ks * 4 + fg));
-    }
-    if (!last) issue(t, 3, kt + 1, sl ^ 1);
-    else if (more) issue(tn, 3, 0, sl ^ 1);
-    // A-bot of K-tile k (issued in R0(k-1)) is followed by: R1(k-1)'s epilogue half and A-top + B of
-    // k+1, this R0's epilogue half and A-bot of k+1
-    const int c_ab = (e_prev ? EB : 0) + (ex1 ? 8 : 0) + (e0 ? EA : 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (wr == 1) vm_wait_q(c_ab);
-    nt_barrier();
-    // ---- M0
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][ks], af[i][ks], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (wr == 0) vm_wait_q(c_ab);
-    if (tq && kt == nk - 2 && tid == 0) {   // publish the next tile (the fetch has retired)
-      if (nk == 2) vm_wait_q(2);              // (K-tile 0: only A-bot of K-tile 1 follows the fetch)
-      asm volatile("" : "+v"(nxt));
-      *s_next = (int)nxt;
-      if ((int)nxt == tiles - 1) __hip_atomic_store(tq, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    nt_barrier();
-    // ---- R1: epilogue rows 64-127 + statistics, A-bot fragments, A-top + B fill of K-tile k+2
-    if (tq && kt == nk - 2) {
-      tn = nwg + __builtin_amdgcn_readfirstlane(*s_next);
-      more = tn < tiles;
-    }
-    if (e0) epilogue256_half<STATS, 1>(acc, a, rC, rS, (pt / gridN) * 256, (pt % gridN) * 256, wr, wc, fr, fg, red);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        af[i][ks] = *reinterpret_cast<const bf16x8*>(sa + swz(wr * 128 + 64 + i * 16 + fr, ks * 4 + fg));
-    const bool ex2 = kt + 2 < nk || more;        // K-tile k+2 exists
-    if (kt + 2 < nk) issue_atb(t, kt + 2, sl);
-    else if (more) issue_atb(tn, kt + 2 - nk, sl);
-    // A-top + B of K-tile k+1 (issued in R1(k-1)) is followed by: this K-tile's two epilogue halves,
-    // A-bot of k+1 and A-top + B of k+2
-    const int c_atb = (e0 ? EA + EB : 0) + (ex1 ? 2 : 0) + (ex2 ? 6 : 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (wr == 1 && ex1) vm_wait_q(c_atb);
-    nt_barrier();
-    // ---- M1
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][ks], af[i][ks], acc[4 + i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (wr == 0 && ex1) vm_wait_q(c_atb);
-    nt_barrier();
-    if (!last) {
-      ++kt;
-      continue;
-    }
-    if (!more) break;
-    // next tile: its K-tiles 0 and 1 are in flight, this one's epilogue runs in its K-tile 0
-    pt = t;
-    t = tn;
-    sb = (sb + nk) & 1;
-    kt = 0;
-    follow = true;
-    tn = t + nwg;
-    more = !tq && tn < tiles;
-  }
-  if (wr == 0) nt_barrier();   // (group 1 ran one barrier behind)
-  const int m0 = (t / gridN) * 256, n0 = (t % gridN) * 256;
-  epilogue256_half<STATS, 0>(acc, a, rC, rS, m0, n0, wr, wc, fr, fg, red);
-  epilogue256_half<STATS, 1>(acc, a, rC, rS, m0, n0, wr, wc, fr, fg, red);
-}
-
-// ---------------------------------------------------------------------------------
 // Weight gradient: P[s][n][k] = sum_{m in split s} G[m][n] * X[m][k]
 // G: [M][ldg] (output-gradient pixel rows), X: [M][ldx] (layer-input pixel rows).
 // Both operands are pixel-major, so the reduction index m is the slow memory
@@ -1163,7 +868,6 @@ struct TNArgs {
   float* P;                // [S][N][K] fp32 partials
   int M, N, K, S, rows_per_split;
   Gather gx;               // gather of the X operand rows / columns
-  int xalign;              // 256x256 kernel: workgroup b = split (b / 8 / tiles) * 8 + b % 8, tile b / 8 % tiles
 };
 
 template <typename T, int GM>
@@ -1296,7 +1000,7 @@ __global__ __launch_bounds__(NT) void gemm_tn_kernel(TNArgs a) {
 
 
 // ---------------------------------------------------------------------------------
-// 256x256 bf16 weight-gradient kernel: P[s][n][k] = sum_{m in split s} G[m][n] X[m][k].
+// 256x256 bf16 weight-gradient kernel (gemm_tn256q_kernel): P[s][n][k] = sum_{m in split s} G[m][n] X[m][k].
 // 8 waves (2 n-groups x 4 k-groups, wave tile 128 n x 64 k), staggered by one barrier as
 // gemm_nt256k64_kernel.  The reduction index m is the ROW index of both operands, so a
 // step is 32 m-rows of each (512-B slab rows: every LDS-DMA instruction moves whole
@@ -1304,11 +1008,15 @@ __global__ __launch_bounds__(NT) void gemm_tn_kernel(TNArgs a) {
 // which makes the transposed ds_read_b64_tr_b16 fragment reads conflict-free).
 // Both operands stream from HBM (nothing L2-resident, unlike the NT weights), so the
 // kernel is bound by bytes in flight per CU: a ring of 5 steps x 32 KB (all 160 KB of
-// LDS) keeps 3 steps (~96 KB) in flight.  Step s is two phases:
-//   A (n-top): reads X frags + G n-top   issues G(s+3)   retires G/X(s+1)
-//   B (n-bot): reads G n-bot             issues X(s+3)
-// A step's data is retired one phase before the first barrier its readers pass; the
-// slot of s+3 is the slot of s-2, last read >= 3 phases earlier.
+// LDS) keeps 4 steps (128 KB) in flight.  Step s is two intervals with one barrier after each:
+//   R: reads every fragment of the step (X: 4 k-frags, G: 8 n-frags = 24 ds_read_b64_tr_b16),
+//      issues G/X(s+4) into the slot step s-1 left (both wave groups finished reading it two
+//      intervals earlier), waits lgkmcnt(0)
+//   M: 32 MFMAs, beside the other wave group's R
+// Step s+1 is retired by a counted vmcnt before the barrier that ends the interval (group 1 in R, group
+// 0 after its MFMAs in M), so every wave has waited before the barrier its readers pass.
+// (A form with two 16-MFMA phases per step and the fill three steps ahead, four barriers per step, gave
+// bitwise-equal slabs and ran 9-13 % slower alone at every step shape: profiles/r06_tn_loop_ab.txt.)
 typedef unsigned long long u64;
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 
@@ -1342,27 +1050,22 @@ XCP_DEV int tswz(int m, int col) {             // byte offset of bf16 column col
   return m * 512 + ((((col >> 3) ^ ((m & 7) << 1))) << 4) + (col & 7) * 2;
 }
 
+XCP_DEV void tn_vm_wait(int n) {   // outstanding LDS-DMA loads allowed to remain (4 per step)
+  if (n >= 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+  else if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+  else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 template <bool BUF>
-__global__ __launch_bounds__(512) void gemm_tn256_kernel(TNArgs a) {
+__global__ __launch_bounds__(512) void gemm_tn256q_kernel(TNArgs a) {
   __shared__ __attribute__((aligned(16))) char smem[T_RING * T_STEP];
   const int gridN = (a.N + 255) / 256, gridK = (a.K + 255) / 256;
   const int tiles = gridN * gridK;
-  // one split's tiles on one XCD, where its row panels are shared through L2.  xalign: workgroups go
-  // to the XCDs round-robin (b % 8), so split (q / tiles) * 8 + b % 8 takes every tile q % tiles of
-  // XCD b % 8's slot row q / tiles -- whole splits per XCD (the grid is padded to 8 splits per slot
-  // row; the padding workgroups return at once).  Otherwise consecutive remapped ids share an XCD,
-  // and a split whose tiles straddle two ranges is read by both XCDs.
-  int sp, t;
-  if (a.xalign) {
-    const int q = blockIdx.x >> 3;
-    sp = (q / tiles) * 8 + (blockIdx.x & 7);
-    t = q % tiles;
-    if (sp >= a.S) return;
-  } else {
-    const int id = xcd_remap(blockIdx.x, gridDim.x);
-    sp = id / tiles;
-    t = id % tiles;
-  }
+  // consecutive remapped ids share an XCD, so a split's tiles find its row panels in one L2 (a split
+  // whose tiles straddle two id ranges is read by both XCDs)
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int sp = id / tiles, t = id % tiles;
   const int n0 = (t / gridK) * 256, k0 = (t % gridK) * 256;
   const int mbeg = sp * a.rows_per_split;
   const int mend = min(a.M, mbeg + a.rows_per_split);
@@ -1390,7 +1093,7 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(TNArgs a) {
                                                                        BUF_DWORD3);
   const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.X), (short)0, BUF_RECORDS,
                                                                        BUF_DWORD3);
-  // operand isG of step st into ring slot sl
+  // operand isG of step st into ring slot sl: 2 instructions
   auto issue = [&](bool isG, int st, int sl) {
     char* d = smem + sl * T_STEP + (isG ? 0 : T_HALF);
 #pragma unroll
@@ -1419,170 +1122,6 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(TNArgs a) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int ns = (mend - mbeg + 31) / 32;
-  // prologue: steps 0..2 in flight, step 0 retired
-#pragma unroll
-  for (int st = 0; st < 3; ++st)
-    if (st < ns) {
-      issue(true, st, st);
-      issue(false, st, st);
-    }
-  if (ns >= 3) wait_vmcnt<8>();
-  else if (ns == 2) wait_vmcnt<4>();
-  else wait_vmcnt<0>();
-  __builtin_amdgcn_s_barrier();
-  if (wr == 1) __builtin_amdgcn_s_barrier();
-
-  const int fr = lane & 15, fg = lane >> 4;
-  const int q4 = fr >> 2, p4 = fr & 3;   // tr read: lane 4q+p reads slab row q, columns 4p..4p+3
-  // fragment of 16 columns at cb: k-slots of lane group fg are slab rows {4fg..4fg+3}
-  // (elements 0-3, r[0]) and 16 + {4fg..} (4-7, r[1]).  The transposed reads are issued
-  // by inline asm: hipcc waits vmcnt(0) before every ds_read_tr builtin while any LDS-DMA
-  // is in flight (draining the ring each phase); the counted vmcnt + barrier protocol
-  // above is what orders them, and lds_fence() retires them before their first use.
-  auto frag = [&](const char* slab, int cb, u64 (&r)[2]) {
-    const int m0r = 4 * fg + q4;
-    const int col = cb + 4 * p4;
-    r[0] = ds_read_tr_asm(slab + tswz(m0r, col));
-    r[1] = ds_read_tr_asm(slab + tswz(m0r + 16, col));
-  };
-  auto b8 = [](const u64 (&r)[2]) { return __builtin_bit_cast(bf16x8, u64x2{r[0], r[1]}); };
-  u64 gr[4][2], xr[4][2];
-  auto mfma4 = [&](int ih) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[ih * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b8(xr[j]), b8(gr[i]), acc[ih * 4 + i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_s_barrier();
-  };
-  int slot = 0, pslot = 3;   // ring slots of step s and of step s + 3
-  for (int s = 0; s < ns; ++s) {
-    const char* sg = smem + slot * T_STEP;
-    const char* sx = sg + T_HALF;
-    const bool pre = s + 3 < ns;
-    // A: n-top
-#pragma unroll
-    for (int j = 0; j < 4; ++j) frag(sx, wc * 64 + j * 16, xr[j]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) frag(sg, wr * 128 + i * 16, gr[i]);
-    if (pre) issue(true, s + 3, pslot);
-    // retire step s+1: loads issued after X(s+1) may stay in flight
-    if (pre) wait_vmcnt<6>();
-    else if (s + 2 < ns) wait_vmcnt<4>();
-    else wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    lds_fence(xr[0], xr[1], xr[2], xr[3]);
-    lds_pin(gr[0], gr[1], gr[2], gr[3]);
-    mfma4(0);
-    // B: n-bot
-#pragma unroll
-    for (int i = 0; i < 4; ++i) frag(sg, wr * 128 + 64 + i * 16, gr[i]);
-    if (pre) issue(false, s + 3, pslot);
-    __builtin_amdgcn_s_barrier();
-    lds_fence(gr[0], gr[1], gr[2], gr[3]);
-    mfma4(1);
-    slot = slot == T_RING - 1 ? 0 : slot + 1;
-    pslot = pslot == T_RING - 1 ? 0 : pslot + 1;
-  }
-  if (wr == 0) __builtin_amdgcn_s_barrier();
-
-  float* P = a.P + (long)sp * a.N * a.K;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int n = n0 + wr * 128 + i * 16 + fr;
-    if (n >= a.N) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = k0 + wc * 64 + j * 16 + 4 * fg;
-      if (k < a.K) *reinterpret_cast<f32x4*>(P + (long)n * a.K + k) = acc[i][j];
-    }
-  }
-}
-
-// Weight-gradient kernel with ONE MFMA phase of 32 per 32-row step and the fill four steps ahead
-// (gemm_tn256q_kernel, the default; XCP_TN_LOOP=1 runs gemm_tn256_kernel's two 16-MFMA phases).  Per step
-// a wave reads all its fragments (X: 4 k-frags, G: 8 n-frags = 24 ds_read_b64_tr_b16) and issues
-// step s+4 into the slot step s-1 left (both wave groups finished reading it two intervals earlier),
-// waits lgkmcnt(0), and its 32 MFMAs run in the next interval beside the other group's reads: two
-// barriers per step instead of four, and 4 x 32 KB of the 5-slot ring in flight instead of 3.
-XCP_DEV void tn_vm_wait(int n) {
-  if (n >= 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-template <bool BUF>
-__global__ __launch_bounds__(512) void gemm_tn256q_kernel(TNArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[T_RING * T_STEP];
-  const int gridN = (a.N + 255) / 256, gridK = (a.K + 255) / 256;
-  const int tiles = gridN * gridK;
-  int sp, t;
-  if (a.xalign) {
-    const int q = blockIdx.x >> 3;
-    sp = (q / tiles) * 8 + (blockIdx.x & 7);
-    t = q % tiles;
-    if (sp >= a.S) return;
-  } else {
-    const int id = xcd_remap(blockIdx.x, gridDim.x);
-    sp = id / tiles;
-    t = id % tiles;
-  }
-  const int n0 = (t / gridK) * 256, k0 = (t % gridK) * 256;
-  const int mbeg = sp * a.rows_per_split;
-  const int mend = min(a.M, mbeg + a.rows_per_split);
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 2, wc = w & 3;
-  const bf16* G = reinterpret_cast<const bf16*>(a.G);
-  const bf16* X = reinterpret_cast<const bf16*>(a.X);
-  const int pc = lane & 31;
-  int rr[2], lc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    rr[i] = 4 * w + 2 * i + (lane >> 5);
-    lc[i] = pc ^ ((rr[i] & 7) << 1);
-  }
-  const void* zero = g_zero16;
-  asm volatile("" : "+v"(zero));
-  auto glds = [](const void* p, char* dst) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)p,
-                                     (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
-  };
-  const __amdgpu_buffer_rsrc_t rG = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.G), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.X), (short)0, BUF_RECORDS,
-                                                                       BUF_DWORD3);
-  auto issue = [&](bool isG, int st, int sl) {   // 2 instructions
-    char* d = smem + sl * T_STEP + (isG ? 0 : T_HALF);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int m = mbeg + st * 32 + rr[i];
-      const int col = (isG ? n0 : k0) + lc[i] * 8;
-      const bool ok = m < mend && col < (isG ? a.N : a.K);
-      char* dst = d + (4 * w + 2 * i) * 512;
-      if constexpr (BUF) {
-        const unsigned o = ok ? (unsigned)(((long)m * (isG ? a.ldg : a.ldx) + col) * 2) : BUF_OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(isG ? rG : rX, (__attribute__((address_space(3))) void*)dst, 16, o,
-                                                 0, 0, 0);
-      } else {
-        const void* src = ok ? (isG ? (const void*)(G + (long)m * a.ldg + col)
-                                    : (const void*)(X + (long)m * a.ldx + col))
-                             : zero;
-        glds(src, dst);
-      }
-    }
-  };
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int ns = (mend - mbeg + 31) / 32;
   // prologue: steps 0..3 in flight, step 0 retired
 #pragma unroll
   for (int st = 0; st < 4; ++st)
@@ -1595,7 +1134,12 @@ __global__ __launch_bounds__(512) void gemm_tn256q_kernel(TNArgs a) {
   if (wr == 1) __builtin_amdgcn_s_barrier();
 
   const int fr = lane & 15, fg = lane >> 4;
-  const int q4 = fr >> 2, p4 = fr & 3;
+  const int q4 = fr >> 2, p4 = fr & 3;   // tr read: lane 4q+p reads slab row q, columns 4p..4p+3
+  // fragment of 16 columns at cb: k-slots of lane group fg are slab rows {4fg..4fg+3}
+  // (elements 0-3, r[0]) and 16 + {4fg..} (4-7, r[1]).  The transposed reads are issued
+  // by inline asm: hipcc waits vmcnt(0) before every ds_read_tr builtin while any LDS-DMA
+  // is in flight (draining the ring each step); the counted vmcnt + barrier protocol
+  // above is what orders them, and lds_fence() retires them before their first use.
   auto frag = [&](const char* slab, int cb, u64 (&r)[2]) {
     const int m0r = 4 * fg + q4;
     const int col = cb + 4 * p4;
@@ -1667,33 +1211,7 @@ namespace {
 // weight gradients on a side stream beside the main stream's dgrad GEMMs and depthwise backward;
 // one 160 KB-LDS workgroup on every CU left those no room, half the CUs (and half the split-K
 // slabs) measured 1.0-1.8 % faster per step for targets 64-192 (profiles/r02_tn_target_sweep.txt).
-constexpr int TN_TARGET_WGS_DEFAULT = 128;
-
-// The A/B switches: first character of environment variable `name`, 0 when it is unset or empty.  A predicate
-// marked "per call" reads its variable at every call (the tests flip those between calls); the ones that keep
-// a `static const` read theirs once per process.
-char env0(const char* name) {
-  const char* e = getenv(name);
-  return e ? e[0] : 0;
-}
-bool tn_xcd_splits() {   // XCP_TN_XCD_SPLITS=1 (A/B; measured -0.3 % in the step, off)
-  static const bool v = env0("XCP_TN_XCD_SPLITS") == '1';
-  return v;
-}
-// The weight-gradient kernel with one 32-MFMA phase per step and the fill 4 steps ahead (gemm_tn256q_kernel):
-// 9-13 % faster alone at every step shape, the partial slabs bitwise equal (profiles/r06_tn_loop_ab.txt).
-// XCP_TN_LOOP=1: gemm_tn256_kernel's two 16-MFMA phases (read per call; A/B)
-bool tn_loop2() { return env0("XCP_TN_LOOP") != '1'; }
-// XCP_TN_XCD_ALIGN=1: whole splits per XCD for outputs of at most 32 tiles (read per call; A/B)
-bool tn_xcd_align() { return env0("XCP_TN_XCD_ALIGN") == '1'; }
-int tn_target_wgs() {   // XCP_TN_TARGET_WGS=<n> overrides the default (A/B of the side-stream share)
-  static const int v = [] {
-    const char* e = getenv("XCP_TN_TARGET_WGS");
-    const int n = e ? atoi(e) : 0;
-    return n > 0 ? n : TN_TARGET_WGS_DEFAULT;
-  }();
-  return v;
-}
+constexpr int TN_TARGET_WGS = 128;
 
 int gpu_cus() {   // compute units of the current device (256 on MI355X)
   static const int cus = [] {
@@ -1705,33 +1223,16 @@ int gpu_cus() {   // compute units of the current device (256 on MI355X)
   return cus;
 }
 
-int nt_big_min_k() {   // XCP_NT_BIG_MINK=<k>: smallest K the automatic choice gives the 256x256 kernel (A/B)
-  static const int v = [] {
-    const char* e = getenv("XCP_NT_BIG_MINK");
-    const int k = e ? atoi(e) : 0;
-    return k > 0 ? k : 384;
-  }();
-  return v;
-}
-
-// Outputs at least 256 wide also take the 256x256 kernel from K = 128 (entry-flow forward GEMMs,
-// tools/kbench.py entrygemm, profiles/r03_entrygemm.txt: 1,401,856 x 256 x 128 / 256 297 -> 241 /
-// 400 -> 318 us, 350,464 x 736 x 256 303 -> 219 us); 128-wide outputs stay on the 128x128 kernel
-// (5,531,904 x 128 x 64 / 128: 459 / 567 us there against 552 / 680 on the 256x256 one).
-// XCP_NT_BIG_N256=0 restores the K >= 384 rule alone (A/B).
-bool nt_big_n256() {
-  static const bool v = env0("XCP_NT_BIG_N256") != '0';
-  return v;
-}
-
-// XCP_NT_SPARSE=0: no sparse last round (every row on the persistent kernel; read per call; A/B)
-bool nt_sparse() { return env0("XCP_NT_SPARSE") != '0'; }
-
+// The automatic choice gives the 256x256 kernel every K >= 384, and outputs at least 256 wide from
+// K = 128 (entry-flow forward GEMMs, tools/kbench.py entrygemm, profiles/r03_entrygemm.txt:
+// 1,401,856 x 256 x 128 / 256 297 -> 241 / 400 -> 318 us, 350,464 x 736 x 256 303 -> 219 us);
+// 128-wide outputs stay on the 128x128 kernel (5,531,904 x 128 x 64 / 128: 459 / 567 us there
+// against 552 / 680 on the 256x256 one).
 bool nt_big(int dtype, int gmode, int M, int N, int K, int tile) {
   if (dtype != XCP_BF16 || gmode != 0 || tile == 1) return false;
   if (tile == 2 || tile == 3) return true;
   if (xcp_cdiv(M, 256) * xcp_cdiv(N, 256) < 256) return false;
-  return K >= nt_big_min_k() || (nt_big_n256() && N >= 256 && K >= 128);
+  return K >= 384 || (N >= 256 && K >= 128);
 }
 
 bool tn_big(int dtype, int gmode, int N, int K, int tile) {
@@ -1739,19 +1240,6 @@ bool tn_big(int dtype, int gmode, int N, int K, int tile) {
   if (dtype != XCP_BF16 || gmode != 0 || tile == 1) return false;
   return tile == 2 || (N >= 256 && K >= 256);
 }
-
-// XCP_NT_LOOP=2: the persistent NT kernel with two MFMA phases per K-tile (gemm_nt256q_kernel) instead of
-// the four of gemm_nt256p_kernel (A/B, read per call)
-bool nt_loop2() { return env0("XCP_NT_LOOP") == '2'; }
-// The 256p kernel's last K-tile multiplies only its first 32-deep half when the rest of it is past K (the
-// 728-channel flow at its 736 pitch: K = 728 / 736, 24 / 32 of the last 64): 32 of the tile's 768 MFMAs
-// per wave skipped, C and the statistics bitwise equal (the skipped products are +0).  XCP_NT_KHALF=0:
-// every K-tile whole (read per call; A/B)
-bool nt_khalf() { return env0("XCP_NT_KHALF") != '0'; }
-// XCP_NT_DYNQ=0: the persistent NT kernel walks its static tile list (A/B; read per call)
-bool nt_dynq() { return env0("XCP_NT_DYNQ") != '0'; }
-// XCP_NT_SPARSE_DGRAD=1 (A/B; read per call)
-bool nt_sparse_dgrad() { return env0("XCP_NT_SPARSE_DGRAD") == '1'; }
 
 // A tile-queue counter is keyed by the (device, stream) of the launch, and each launch relies on being
 // its counter's only user between its first fetch and its last (which resets it).  Launches on one
@@ -1764,7 +1252,6 @@ bool stream_capturing(hipStream_t st) {
 }
 // tile-queue slot + 1 of (device, stream) for gemm_nt256p_kernel (0: static walk, past 64 streams)
 int nt_tq_slot(hipStream_t st) {
-  if (!nt_dynq()) return 0;
   static std::mutex mu;
   static std::vector<std::pair<int, hipStream_t>> slots;
   int dev = 0;
@@ -1806,24 +1293,23 @@ int xcp_gemm_nt(int dtype, const void* A, long lda, const void* B, long ldb, voi
   if (tile < 0 || tile > 4) return XCP_EINVAL;
   if (!gather_ok(gmode, M, K, lda, gH, gW, gOH, gOW, gS)) return XCP_EINVAL;
   NTArgs a{A, lda, B, ldb, C, ldc, M, N, K, stats, Gather{gmode, gH, gW, gOH, gOW, gS > 0 ? gS : 1, gC}};
-  a.khalf = nt_khalf() ? 1 : 0;
   if (nt_big(dtype, gmode, M, N, K, tile)) {
     // automatic choice (tile 0): the persistent kernel; tile 4: the automatic choice with the
     // one-shot kernel (A/B)
     const bool persist = tile == 3 || tile == 0;
     // One 256x256 tile per CU per round.  When the last round would be less than 3/4 full
     // (1,083 tiles = 4.23 rounds in the middle flow), its rows go to the 128x128 kernel
-    // instead: four times as many, smaller tiles, one launch after the full rounds
+    // instead: four times as many, smaller tiles, one launch after the full rounds; +0.5 % in the
+    // step, profiles/r04_nt_sparse_ab.txt
     // (tile 0 / 4 only; tile 2 pins the one-shot 256 kernel for every row, tile 3 the persistent one).
     const int gridN = xcp_cdiv(N, 256), gridM = xcp_cdiv(M, 256), tiles = gridM * gridN;
     const int cus = gpu_cus();
     int mb = gridM;
     // (calls that take the tile queue keep every row on the persistent kernel: the queue spreads the last
-    // round's tiles over whichever workgroups finish first; +0.2 % in the step, profiles/r05_nt_dynq_ab.txt;
-    // XCP_NT_SPARSE_DGRAD=1 moves their sparse last round to the 128x128 kernel as before)
-    const bool queued = tile == 0 && K >= 128 && !stats && nt_dynq();
+    // round's tiles over whichever workgroups finish first; +0.2 % in the step, profiles/r05_nt_dynq_ab.txt)
+    const bool queued = tile == 0 && K >= 128 && !stats;
     const bool partial = tiles > cus && tiles % cus != 0 && (tiles % cus) * 4 < cus * 3;   // last round < 3/4 full
-    if ((tile == 0 || tile == 4) && nt_sparse() && (!queued || nt_sparse_dgrad()) && partial)
+    if ((tile == 0 || tile == 4) && !queued && partial)
       mb = (tiles / cus) * cus / gridN;
     NTArgs big = a;
     big.M = min(M, mb * 256);
@@ -1836,12 +1322,7 @@ int xcp_gemm_nt(int dtype, const void* A, long lda, const void* B, long ldb, voi
       // the static XCD-ordered walk: with the queue they measured 1 % slower); K >= 128: the counter's
       // fetch retires within two K-tiles
       big.tqs = K >= 128 && !stats && !stream_capturing(stream) ? nt_tq_slot(stream) : 0;
-      if (K > 64 && nt_loop2()) {   // two MFMA phases per K-tile, fill 1.5 K-tiles ahead
-        if (stats)
-          hipLaunchKernelGGL(gemm_nt256q_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
-        else
-          hipLaunchKernelGGL(gemm_nt256q_kernel<false>, dim3(grid), dim3(512), 0, stream, big);
-      } else if (stats)
+      if (stats)
         hipLaunchKernelGGL(gemm_nt256p_kernel<true>, dim3(grid), dim3(512), 0, stream, big);
       else
         hipLaunchKernelGGL(gemm_nt256p_kernel<false>, dim3(grid), dim3(512), 0, stream, big);
@@ -1891,14 +1372,11 @@ int xcp_gemm_tn_rows_per_split(int dtype, int gmode, int M, int N, int K, int ti
   const bool big = tn_big(dtype, gmode, N, K, tile);
   const int tsz = big ? 256 : 128, align = big ? 64 : 32;
   const int tiles = xcp_cdiv(N, tsz) * xcp_cdiv(K, tsz);
-  const int target = big ? tn_target_wgs() : 1024, min_rows = big ? 512 : 256;
+  const int target = big ? TN_TARGET_WGS : 1024, min_rows = big ? 512 : 256;
   int S = target / (tiles > 0 ? tiles : 1);
   S = S < 1 ? 1 : S;
-  // XCP_TN_XCD_SPLITS=1: for few output tiles a multiple of 8 splits, so that with the kernel's
-  // XCD remap every XCD holds whole splits and a split's row panels are shared by all of its tiles
-  // in one L2 (9 tiles x 14 splits = 126 workgroups put most splits across two XCDs).  Measured in
-  // the step: 399.6-400.4 vs 400.7-401.3 clips/s with the plain count (profiles/r03_ab3.txt): off.
-  if (big && tiles <= 16 && S >= 4 && tn_xcd_splits()) S = (S + 4) / 8 * 8;
+  // (a multiple of 8 splits for few output tiles, so that every XCD holds whole splits, measured
+  // 399.6-400.4 against 400.7-401.3 clips/s with this plain count: profiles/r03_ab3.txt)
   const int smax = xcp_cdiv(M, min_rows);
   S = S < smax ? S : smax;
   int rps = xcp_cdiv(M, S);
@@ -1918,19 +1396,12 @@ int xcp_gemm_tn(int dtype, const void* G, long ldg, const void* X, long ldx, flo
   TNArgs a{G, ldg, X, ldx, P, M, N, K, S, rows_per_split, Gather{gmode, gH, gW, gOH, gOW, gS > 0 ? gS : 1, gC}};
   if (tn_big(dtype, gmode, N, K, tile)) {
     if (rows_per_split % 32) return XCP_EINVAL;
-    const int tiles = xcp_cdiv(N, 256) * xcp_cdiv(K, 256);
-    a.xalign = tiles <= 32 && S >= 2 && tn_xcd_align();
-    const dim3 grid(a.xalign ? 8 * xcp_cdiv(S, 8) * tiles : tiles * S);
+    const dim3 grid(xcp_cdiv(N, 256) * xcp_cdiv(K, 256) * S);
     const bool buf = ((long)(M - 1) * ldg + N) * 2 <= BUF_LIMIT && ((long)(M - 1) * ldx + K) * 2 <= BUF_LIMIT;
-    if (tn_loop2()) {
-      if (buf)
-        hipLaunchKernelGGL(gemm_tn256q_kernel<true>, grid, dim3(512), 0, stream, a);
-      else
-        hipLaunchKernelGGL(gemm_tn256q_kernel<false>, grid, dim3(512), 0, stream, a);
-    } else if (buf)
-      hipLaunchKernelGGL(gemm_tn256_kernel<true>, grid, dim3(512), 0, stream, a);
+    if (buf)
+      hipLaunchKernelGGL(gemm_tn256q_kernel<true>, grid, dim3(512), 0, stream, a);
     else
-      hipLaunchKernelGGL(gemm_tn256_kernel<false>, grid, dim3(512), 0, stream, a);
+      hipLaunchKernelGGL(gemm_tn256q_kernel<false>, grid, dim3(512), 0, stream, a);
     return (int)hipGetLastError();
   }
   const int grid = xcp_cdiv(N, 128) * xcp_cdiv(K, 128) * S;

@@ -116,14 +116,16 @@ def test_dma_pipelines_not_drained_by_compiler_waits(tmp_path):
     vmcnt(0) inside their loops (hipcc adds one ahead of an LDS access it cannot prove disjoint from an
     in-flight DMA -- a ds_read_tr builtin, an access after a second __shared__ object gave the accesses
     alias scopes, a compiler-visible global load in the prologue -- and it drains the look-ahead every
-    iteration).  GEMMs (NT 256x256, both TN 256x256 loops), stem conv2 forward / dgrad / weight gradient, every
-    form of the depthwise backward (plain ring reads of the one LDS object).  The depthwise backward is also
-    counted: 5 forms x 3 activations x 2 dtypes, so a form no call reaches cannot come back unnoticed."""
+    iteration).  GEMMs (NT 256x256 one-shot and persistent, TN 256x256), stem conv2 forward / dgrad / weight
+    gradient, every form of the depthwise backward (plain ring reads of the one LDS object).  Two families are
+    also counted, so a form no call reaches cannot come back unnoticed: the depthwise backward (5 forms x 3
+    activations x 2 dtypes) and the 256x256 GEMMs (gemm_nt256p_kernel<STATS>, gemm_nt256k64_kernel<BUF>,
+    gemm_tn256q_kernel<BUF>: six, and no other gemm_nt256* / gemm_tn256* kernel)."""
     import re
     hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
     csrc = os.path.join(REPO, "multimodal-deepfake-detection_amd", "xcp", "csrc")
     checks = {
-        "gemm.hip": lambda n: re.search(r"gemm_(nt256p|nt256k64|tn256q?)_kernel", n),
+        "gemm.hip": lambda n: re.search(r"gemm_(nt256p|nt256k64|tn256q)_kernel", n),
         "conv3.hip": lambda n: "conv3x3" in n,
         # dw_bwd_lds_kernel<T, ACT, RES, SKIP, BNRES>
         "dwconv.hip": lambda n: re.search(r"dw_bwd_lds_kernelI(DF16b|f)Li\dELb[01]ELb[01]ELb[01]E", n),
@@ -144,3 +146,10 @@ def test_dma_pipelines_not_drained_by_compiler_waits(tmp_path):
         if f == "dwconv.hip":
             defined = re.findall(r"^(_Z\S*dw_bwd_lds_kernel\S*):", out.read_text(), re.M)
             assert len(defined) == 30 and len(found) == 30, sorted(defined)
+        if f == "gemm.hip":
+            # every symbol with gemm_nt256 / gemm_tn256 in its name: kernel<bool> of the anonymous namespace
+            defined = re.findall(r"^(_Z\S*gemm_(?:nt|tn)256\S*):", out.read_text(), re.M)
+            names = sorted(re.sub(r"^_ZN12_GLOBAL__N_1\d+|EEEvNS_6[NT]{2}ArgsE$", "", d) for d in defined)
+            want = [f"{k}ILb{b}" for k in ("gemm_nt256k64_kernel", "gemm_nt256p_kernel", "gemm_tn256q_kernel")
+                    for b in (0, 1)]
+            assert names == want and len(found) == 6, sorted(defined)

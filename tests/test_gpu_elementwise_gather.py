@@ -8,7 +8,7 @@ pitch wider than K, M = 1, strides 1 to 3.  Every element of A the gather must n
 every gathered operand here, sits between NaN margins; C and the partial sums start as NaN.
 gemm_nt, modes 2 / 3 (conv2 forward and input gradient): one output pixel, one visible tap per pixel, M-tiles
 that span frames, five frames in one tile, gC 8 / 32 / 64.
-gemm_tn: every slab P[s] of the dense kernels (128x128; 256x256 in both XCP_TN_LOOP forms) at splits of 32 and
+gemm_tn: every slab P[s] of the dense kernels (128x128; 256x256) at splits of 32 and
 64 rows with a ragged last one, of the gathered kernel in modes 1 and 2 at the library's own split and at 32
 rows; ops.weight_grad end to end, plain and accumulating.
 The gather geometry guard of xcp_gemm_nt / xcp_gemm_tn: inconsistent calls are rejected before any launch.
@@ -114,19 +114,17 @@ def run_slabs(ops, G, X, M, N, K, rps, case, Xg=None, **kw):
     record(case, f"P[{S}]", E.assert_f32_sum(P.view(S, N, K), ref, ab, n, tag=case))
 
 
-@pytest.mark.parametrize("form", [("bf16", 1, 32, None), ("bf16", 1, 64, None), ("fp32", 1, 32, None),
-                                  ("fp32", 1, 64, None), ("bf16", 2, 64, "0"), ("bf16", 2, 64, "1")], ids=str)
+@pytest.mark.parametrize("form", [("bf16", 1, 32), ("bf16", 1, 64), ("fp32", 1, 32), ("fp32", 1, 64),
+                                  ("bf16", 2, 64)], ids=str)
 @pytest.mark.parametrize("shape", E.TN_SLAB_SHAPES, ids=str)
-def test_gemm_tn_dense_slabs(ops, gpu, monkeypatch, shape, form):
-    """gemm_tn_kernel (tile 1) and the 256x256 kernels (tile 2: gemm_tn256q_kernel, and gemm_tn256_kernel under
-    XCP_TN_LOOP=1) at 4 to 10 splits with a ragged last one: mbeg / mend of every split"""
+def test_gemm_tn_dense_slabs(ops, gpu, shape, form):
+    """gemm_tn_kernel (tile 1) and the 256x256 kernel (tile 2: gemm_tn256q_kernel) at 4 to 10 splits with a
+    ragged last one: mbeg / mend of every split"""
     M, N, K = shape
-    dt, tile, rps, loop = form
+    dt, tile, rps = form
     assert (tile, rps) in E.TN_SLAB_FORMS
-    if loop is not None:
-        monkeypatch.setenv("XCP_TN_LOOP", loop)
     G, X = (t.to(gpu) for t in E.gemm_tn_inputs(M, N, K, DTS[dt]))
-    run_slabs(ops, G, X, M, N, K, rps, f"tn dense {shape} {dt} tile{tile} rps{rps} loop{loop}", tile=tile)
+    run_slabs(ops, G, X, M, N, K, rps, f"tn dense {shape} {dt} tile{tile} rps{rps}", tile=tile)
 
 
 TN_GATHER_CASES = [(1, s) for s in E.GATHER1_SHAPES] + [(2, s) for s in E.IM2COL_SHAPES]

@@ -193,28 +193,6 @@ def test_gemm_tn(ops, gpu, dt, M, N, K, tile):
     assert rel_err(acc.view(N, K), ref + base.view(N, K)) < (1e-5 if dt == torch.float32 else 1e-3)
 
 
-@pytest.mark.parametrize("M,N,K", [(92416, 728, 728), (20000, 1024, 736), (9000, 256, 512)])
-def test_gemm_tn_xcd_align_bitwise(ops, gpu, monkeypatch, M, N, K):
-    """Whole weight-gradient splits per XCD (XCP_TN_XCD_ALIGN=1: padded grid, another workgroup ->
-    (split, tile) map) computes every split's slab in the same order: slabs bitwise equal."""
-    g = torch.Generator(device=gpu).manual_seed(M + N)
-    G = torch.randn(M, N, device=gpu, generator=g).bfloat16()
-    X = torch.randn(M, K, device=gpu, generator=g).bfloat16()
-    rps = ops._lib.call("xcp_gemm_tn_rows_per_split", 1, 0, M, N, K, 0)
-    S = (M + rps - 1) // rps
-    outs = []
-    for v in ("0", "1"):
-        monkeypatch.setenv("XCP_TN_XCD_ALIGN", v)
-        P = torch.full((S * N * K,), float("nan"), device=gpu)
-        ops.gemm_tn(G, X, P, M, N, K, S, rps)
-        torch.cuda.synchronize()
-        outs.append(P)
-    assert not torch.isnan(outs[1]).any()
-    assert torch.equal(outs[0], outs[1])
-    ref = G.float().t() @ X.float()
-    assert rel_err(outs[1].view(S, N, K).sum(0), ref) < 1e-3
-
-
 @pytest.mark.parametrize("S,L", [(1, 5), (3, 1001), (28, 728 * 728), (768, 728 * 9), (2560, 128 * 9), (40, 2304),
                                  (17, 6), (300, 7)])
 @pytest.mark.parametrize("accumulate", [False, True])
@@ -1114,19 +1092,14 @@ def test_fused_adam_clip_load_state_dict_resume(ops, gpu):
         torch.testing.assert_close(opt_a.state[p]["exp_avg"], opt_b.state[q]["exp_avg"], rtol=1e-5, atol=1e-7)
 
 
-@pytest.mark.parametrize("loop", ["4", "2"])
 @pytest.mark.parametrize("M,N,K,ref", [(92416, 736, 736, 2), (5120 * 9, 1024, 736, 2), (2048 * 7 + 256, 512, 64, 2),
                                        (256 * 506 + 77, 256, 200, 2), (256 * 600 + 77, 256, 448, 2),
                                        (256 * 300 + 5, 512, 128, 2)])
-def test_gemm_nt_persistent_bitwise(ops, gpu, monkeypatch, M, N, K, ref, loop):
-    """The persistent 256x256 kernel (tile 3, every row on it; loop 4: gemm_nt256p_kernel, loop 2:
-    gemm_nt256q_kernel's two MFMA phases per K-tile) computes every tile with the one-shot kernel's
-    MFMA order: identical output bits against tile 2 (the one-shot kernel for every row), across
-    several tiles per workgroup (the prefetch / epilogue overlap must not change a value).  The BN
-    statistics are bitwise too for loop 4; loop 2 reduces each 64-row half of a wave's rows over the
-    wave and adds the two (its epilogue runs in two halves), so its sums differ by fp32 rounding only
-    (1e-6 relative here).  K = 128: two K-tiles per tile, the shortest the two-phase loop runs."""
-    monkeypatch.setenv("XCP_NT_LOOP", loop)
+def test_gemm_nt_persistent_bitwise(ops, gpu, M, N, K, ref):
+    """The persistent 256x256 kernel (tile 3, every row on gemm_nt256p_kernel) computes every tile with
+    the one-shot kernel's MFMA order: identical output bits against tile 2 (the one-shot kernel for
+    every row), across several tiles per workgroup (the prefetch / epilogue overlap must not change a
+    value).  The BN statistics are bitwise too.  K = 64: one K-tile per tile; K = 128: two."""
     tile = 3
     g = torch.Generator(device=gpu).manual_seed(M + N)
     A = torch.randn(M, K, device=gpu, generator=g).bfloat16()
@@ -1140,17 +1113,13 @@ def test_gemm_nt_persistent_bitwise(ops, gpu, monkeypatch, M, N, K, ref, loop):
         outs.append((C, part))
     torch.cuda.synchronize()
     assert torch.equal(outs[0][0], outs[1][0])
-    if loop == "4":
-        assert torch.equal(outs[0][1], outs[1][1])
-    else:
-        assert not torch.isnan(outs[1][1]).any()
-        torch.testing.assert_close(outs[1][1], outs[0][1], rtol=1e-6, atol=1e-6 * outs[0][1].abs().max().item())
+    assert torch.equal(outs[0][1], outs[1][1])
 
 
 @pytest.mark.parametrize("M,N,K", [(92416, 736, 736), (256 * 600 + 77, 256, 448), (5120 * 9, 1024, 736)])
 def test_gemm_nt_persistent_tile_queue_bitwise(ops, gpu, M, N, K):
     """Calls without BN statistics (the backward's input gradients) take the persistent kernel's tiles
-    from a per-stream queue (XCP_NT_DYNQ): identical bits against the one-shot kernel, over repeated
+    from a per-stream queue: identical bits against the one-shot kernel, over repeated
     launches (each launch's last fetch resets the counter) and on two streams at once (one counter
     each)."""
     g = torch.Generator(device=gpu).manual_seed(M + 3 * N)
@@ -1290,48 +1259,43 @@ def test_sep_fwd_rejects_unsupported(ops, gpu):
 
 
 @pytest.mark.parametrize("M,N,K", [(92416, 728, 728), (3000, 296, 520), (32 * 7 + 5, 256, 264), (20000, 1024, 256)])
-def test_gemm_tn_loops_bitwise(ops, gpu, monkeypatch, M, N, K):
-    """The weight-gradient kernel with one 32-MFMA phase per step and the fill four steps ahead
-    (gemm_tn256q_kernel, the default) against gemm_tn256_kernel (XCP_TN_LOOP=1): the same MFMA order per
-    accumulator, so the fp32 partial slabs are bitwise equal (ragged M / N / K, splits shorter than
-    the ring)."""
+def test_gemm_tn256_vs_fp32(ops, gpu, M, N, K):
+    """The 256x256 weight-gradient kernel (gemm_tn256q_kernel, tile 2: one 32-MFMA phase per step, the fill
+    four steps ahead) at ragged M / N / K and splits shorter than the ring: every slab element written,
+    the slabs' sum against the fp32 product."""
     g = torch.Generator(device=gpu).manual_seed(M + N + K)
     G = torch.randn(M, N, device=gpu, generator=g).bfloat16()
     X = torch.randn(M, K, device=gpu, generator=g).bfloat16()
     rps = ops._lib.call("xcp_gemm_tn_rows_per_split", 1, 0, M, N, K, 2)
     S = (M + rps - 1) // rps
-    outs = []
-    for form in ("1", "2"):
-        monkeypatch.setenv("XCP_TN_LOOP", form)
-        P = torch.full((S * N * K,), float("nan"), device=gpu)
-        ops.gemm_tn(G, X, P, M, N, K, S, rps, tile=2)
-        torch.cuda.synchronize()
-        outs.append(P)
-    assert not torch.isnan(outs[1]).any()
-    assert torch.equal(outs[0], outs[1])
+    P = torch.full((S * N * K,), float("nan"), device=gpu)
+    ops.gemm_tn(G, X, P, M, N, K, S, rps, tile=2)
+    torch.cuda.synchronize()
+    assert not torch.isnan(P).any()
     ref = (G.float().t() @ X.float())
-    got = outs[1].view(S, N, K).sum(0)
+    got = P.view(S, N, K).sum(0)
     torch.testing.assert_close(got, ref, rtol=2e-3, atol=2e-3 * ref.abs().max().item())
 
 
 @pytest.mark.parametrize("M,N,K,stats", [(92416, 736, 736, True), (92416, 736, 736, False), (256 * 100 + 7, 768, 200, True),
                                          (256 * 100 + 7, 768, 392, False), (256 * 300 + 5, 512, 128, False),
                                          (256 * 100 + 7, 736, 728, True)])
-def test_gemm_nt_khalf_bitwise(ops, gpu, monkeypatch, M, N, K, stats):
-    """XCP_NT_KHALF (0 in the reference run, 1 = the default): a last K-tile of the persistent kernel with
-    K % 64 in (0, 32] multiplies its first 32-deep half only (K = 200 / 392 / 728 / 736) -- with the static
-    walk (statistics) and with the tile queue (none): output and statistics bits identical to the reference
-    run for every row (the default persistent kernel, same sparse last round on the 128x128 kernel)."""
+def test_gemm_nt_khalf_bitwise(ops, gpu, M, N, K, stats):
+    """A last K-tile of the persistent kernel with K % 64 in (0, 32] multiplies its first 32-deep half only
+    (K = 200 / 392 / 728 / 736; K = 128 has no partial K-tile) -- with the static walk (statistics) and with
+    the tile queue (none).  The reference is the one-shot kernel (tile 2), which multiplies every K-tile
+    whole: the half-K skip exists only in gemm_nt256p_kernel.  Every row runs on the persistent kernel
+    (tile 3), three times (the tile queue's counter must be reset between launches): output and statistics
+    bits identical to the reference for every row."""
     g = torch.Generator(device=gpu).manual_seed(M + N + K)
     A = torch.randn(M, K, device=gpu, generator=g).bfloat16()
     B = (torch.randn(N, K, device=gpu, generator=g) / K ** 0.5).bfloat16()
     R = ops.nt_stat_rows(M)
     outs = []
-    for i in range(3):   # (switched on twice: the tile queue's counter must be reset)
-        monkeypatch.setenv("XCP_NT_KHALF", "1" if i else "0")
+    for tile in (2, 3, 3, 3):
         C = torch.full((M, N), float("nan"), device=gpu, dtype=torch.bfloat16)
         part = torch.full((R, 2, N), float("nan"), device=gpu) if stats else None
-        ops.gemm_nt(A, B, C, M, N, K, stats=part, tile=0)
+        ops.gemm_nt(A, B, C, M, N, K, stats=part, tile=tile)
         torch.cuda.synchronize()
         outs.append((C, part))
     torch.cuda.synchronize()

@@ -27,13 +27,14 @@ def patched():
     s = open(os.path.join(SRC, "gemm.hip")).read()
     s = s.replace('#include "common.h"\n', '#include "' + os.path.join(SRC, "common.h") + '"\n'
                   "__device__ long long* g_ph;\n", 1)
-    old = """  auto sync_mfma = [&](int ih, const bf16x8 (&b)[2][2], int jh) {
+    old = """  auto sync_mfma = [&](int ih, const bf16x8 (&b)[2][2], int jh, auto nks) {
     __builtin_amdgcn_s_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    mfma_q(ih, b, jh);
+    mfma_q(ih, b, jh, nks);
     __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
   };
 
@@ -45,7 +46,7 @@ def patched():
     const long long c = clock64();
     if (rec_ && ph_ >= %d && ph_ < %d) ph_buf[(ph_ - %d) * NS_ + k] = c;
   };
-  auto sync_mfma = [&](int ih, const bf16x8 (&b)[2][2], int jh) {
+  auto sync_mfma = [&](int ih, const bf16x8 (&b)[2][2], int jh, auto nks) {
     stamp_(0);
     __builtin_amdgcn_s_barrier();
     stamp_(1);
@@ -53,7 +54,7 @@ def patched():
     __builtin_amdgcn_sched_barrier(0);
     stamp_(2);
     __builtin_amdgcn_s_setprio(1);
-    mfma_q(ih, b, jh);
+    mfma_q(ih, b, jh, nks);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     stamp_(3);
@@ -66,7 +67,7 @@ def patched():
     assert old in s
     s = s.replace(old, new, 1)
     s = s.replace("__device__ long long* g_ph;\n", "__device__ long long* g_ph;\n#define NS_ %d\n" % NS, 1)
-    k0 = s.index("auto ktile = [&](int kt, auto first) {")
+    k0 = s.index("auto ktile = [&](int kt, auto mode, auto nks) {")
     body = s[k0:]
     for h in range(3):
         a = "      if (nxt) issue(%d, kt + 1);\n" % h

@@ -13,10 +13,22 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "multimodal-deepfake-detection_amd"), REPO]
 from xcp import ops  # noqa: E402
-from nt_env_ab import timeit  # noqa: E402
 
 SHAPES = [(92416, 736, 736, True), (92416, 736, 736, False), (350464, 736, 736, True), (30720, 736, 736, True),
           (350464, 256, 736, False), (92416, 1024, 736, True)]
+
+
+def timeit(fn, iters=20, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters * 1e3
 
 
 def main():
