@@ -402,6 +402,37 @@ int xcp_lstm_bwd_state(const float* dout, const float* dhn, const float* dcn, co
                        const float* cst, const float* gates, float* dgates, float* dh0, float* dc0, float* work,
                        const int* lens, int B, int T, int H, int kernel, xcp_stream_t stream);
 
+/* ---- both directions of time ----
+ * Reference: nn.LSTM(I, H, 1, batch_first=True, bidirectional=True), over packed input when lens is given
+ * (pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length = T)).
+ * dirs is a mask: 1 = the forward direction only, 2 = the reverse direction only, 3 = both; D = 1, 1, 2
+ * slots.  Any other mask is XCP_EINVAL.  Everything per direction is dense and stacked on a leading axis of
+ * D slots (slot 0 is the forward direction unless dirs = 2):
+ *   whh [D][4H][H], whhT [D][H][4H], bih / bhh [D][4H], xproj / gates / dgates [D][B*T][4H],
+ *   hprev / cst [D][B][T][H], h0 / c0 / hn / cn / dh0 / dc0 / dhn / dcn [D][B][H] (nn.LSTM's own layout),
+ * while out / dout are [B][T][D*H] as nn.LSTM lays them, slot d in columns d*H .. d*H + H - 1: the kernels
+ * write and read the interleaved tensor in place.
+ * The reverse direction of clip b (L = lens[b] clamped to [0, T], or T) visits t = L - 1 .. 0: the state
+ * entering time t is that of t + 1, and h0[1][b] / c0[1][b] (or zero) at t = L - 1, which is also the saved
+ * hprev[1][b][L - 1]; hn[1] / cn[1] are the state after time 0 (for L = 0, h0[1] / c0[1] or zero); rows
+ * t >= L of out and hprev are zero.  Its backward walks t = 0 .. L - 1 with dhn[1] / dcn[1] entering at
+ * t = 0; dh0[1][b] = sum_j dgates_{L-1}[b][j] W_hh_r[j][:] and dc0[1][b] = dc_{L-1} f_{L-1} (for L = 0,
+ * dhn / dcn).  Direction 0 is bit-identical to the entries above.
+ * h0 / c0 are nullable together (half a state is XCP_EINVAL), lens is nullable, dh0 / dc0 each.  Kernel by
+ * shape: register-resident (H = 64 / 128), per-step (H = 256 / 512 / 1024, B <= 32) or generic, both
+ * directions in the same launches; never the persistent, gather or clip-grouped kernels.
+ * xcp_lstm_dir_needs_whhT(B, H, kernel): 1 when the generic kernel runs (it reads whhT).
+ * xcp_lstm_bwd_dir's work: D * (B*H + 4*H*H) floats (per-step kernels: a carry and W_hh^T per direction). */
+int xcp_lstm_dir_needs_whhT(int B, int H, int kernel);
+/* nn.LSTM(I, H, 1, batch_first=True, bidirectional=True) forward recurrence */
+int xcp_lstm_fwd_dir(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh,
+                     const float* h0, const float* c0, float* out, float* hprev, float* cst, float* gates, float* hn,
+                     float* cn, const int* lens, int B, int T, int H, int kernel, int dirs, xcp_stream_t stream);
+/* backward of nn.LSTM(I, H, 1, batch_first=True, bidirectional=True) */
+int xcp_lstm_bwd_dir(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* c0,
+                     const float* cst, const float* gates, float* dgates, float* dh0, float* dc0, float* work,
+                     const int* lens, int B, int T, int H, int kernel, int dirs, xcp_stream_t stream);
+
 /* ---- diagnostic (bench.py only; no reference counterpart) ----
  * blocks workgroups (one per CU) each run `iters` x 4 back-to-back bf16 MFMAs; out: DEVICE int64
  * [2 * blocks + 256]: out[2b] = shader cycles of block b's loop, out[2b + 1] = 100 MHz real-time

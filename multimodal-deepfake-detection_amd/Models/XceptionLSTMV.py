@@ -18,15 +18,24 @@ from .Xception import xception
 
 
 class XceptionLSTMV(nn.Module):
-    def __init__(self, hidden_dim, pretrained=True):
+    def __init__(self, hidden_dim, pretrained=True, bidirectional=False):
+        """``bidirectional=True``: ``lstm`` reads each clip in both directions of time and the head is fed
+        ``cat(h_n[0], h_n[1])`` (the forward state after the clip's last frame, the reverse state after its
+        first), so ``fc_layers[0]`` is ``Linear(2 * hidden_dim, 1024)``.  The default is the reference's model,
+        unchanged."""
         super(XceptionLSTMV, self).__init__()
         self.feature_extractor = xception(pretrained=pretrained)
         self.feature_extractor.fc = nn.Identity()
         for param in self.feature_extractor.parameters():
             param.requires_grad = False
-        self.lstm = LSTM(input_size=2048, hidden_size=hidden_dim, num_layers=1, batch_first=True)
+        self.bidirectional = bool(bidirectional)
+        if self.bidirectional:
+            self.lstm = LSTM(input_size=2048, hidden_size=hidden_dim, num_layers=1, batch_first=True,
+                             bidirectional=True)
+        else:
+            self.lstm = LSTM(input_size=2048, hidden_size=hidden_dim, num_layers=1, batch_first=True)
         self.fc_layers = nn.Sequential(
-            nn.Linear(hidden_dim, 1024), nn.ReLU(), nn.Dropout(0.3),
+            nn.Linear(2 * hidden_dim if self.bidirectional else hidden_dim, 1024), nn.ReLU(), nn.Dropout(0.3),
             nn.Linear(1024, 1024), nn.ReLU(), nn.Dropout(0.3),
             nn.Linear(1024, 1024), nn.ReLU(), nn.Dropout(0.3),
             nn.Linear(1024, 1024), nn.ReLU(), nn.Dropout(0.3),
@@ -50,7 +59,10 @@ class XceptionLSTMV(nn.Module):
         """``features`` [B,T,2048] -> clip probability [B,1].  With ``seq_lengths`` ([B], the loaders'
         per-clip frame counts of the zero-padded batch; train_visual.py:111) the head is fed the LSTM
         state at each clip's own last frame instead of the state after the padding."""
-        if seq_lengths is not None:
+        if self.bidirectional:   # both summaries: forward after the last real frame, reverse after the first
+            _, (h_n, _) = self.lstm(features, lengths=seq_lengths)
+            lstm_out = torch.cat((h_n[0], h_n[1]), dim=1)
+        elif seq_lengths is not None:
             _, (h_n, _) = self.lstm(features, lengths=seq_lengths)
             lstm_out = h_n[0]
         else:
@@ -65,6 +77,9 @@ class XceptionLSTMV(nn.Module):
         the probability of the clip so far.  A clip with no frame in this chunk (device ``seq_lengths`` entry
         0) keeps its state, so its probability stays that of its last real frame.  ``forward`` keeps its
         two-argument signature (tests pin it), so the state has a method of its own."""
+        if self.bidirectional:
+            raise ValueError("forward_state: a bidirectional model cannot be fed in chunks of frames (its reverse "
+                             "direction starts from the clip's last frame); use forward on the whole clip")
         _, (h_n, c_n) = self.lstm(features, state, lengths=seq_lengths)
         dense_out = self.fc_layers(h_n[0])
         return self.sigmoid(self.fc_out(dense_out)), (h_n, c_n)

@@ -102,6 +102,9 @@ SIGNATURES = {
     "xcp_lstm_state_needs_whhT": [I, I, I],
     "xcp_lstm_fwd_state": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "xcp_lstm_bwd_state": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
+    "xcp_lstm_dir_needs_whhT": [I, I, I],
+    "xcp_lstm_fwd_dir": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "xcp_lstm_bwd_dir": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "xcp_clock_probe": [P, I, I, P],
     "xcp_stream_copy": [P, P, L, P],
     "xcp_comm_proxy": [P, P, L, I, ctypes.c_longlong, P, P],
@@ -113,7 +116,7 @@ SIZE_QUERIES = {"xcp_permute3_blocks", "xcp_sep_fwd_parts", "xcp_gemm_tn_rows_pe
                 "xcp_colreduce_groups", "xcp_unit_bwd_rows_per_split",
                 "xcp_conv1_wgrad_parts", "xcp_conv1_wgrad_fused", "xcp_conv1_fwd_parts", "xcp_lstm_needs_whhT", "xcp_conv3x3_parts", "xcp_conv3x3_wgrad_parts",
                 "xcp_maxpool_bwd_bnred_parts", "xcp_lstm_sync_error", "xcp_lstm_varlen_needs_whhT",
-                "xcp_lstm_state_needs_whhT"}
+                "xcp_lstm_state_needs_whhT", "xcp_lstm_dir_needs_whhT"}
 
 _lib = None
 

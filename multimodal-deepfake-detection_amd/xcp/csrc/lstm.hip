@@ -49,6 +49,25 @@
 // carried into h0 / c0 (and dh0 / dc0 back into dh_n / dc_n) is bit-identical to the whole run in out,
 // h_n, c_n, cst and dgates (tests/test_gpu_lstm_state.py).  A call with a state never takes the
 // persistent, gather or clip-grouped kernels: nothing new polls.  h0 / c0 must not alias h_n / c_n.
+//
+// Directions.  The same three families are templates on `bool DR` as well: DR = false is the kernel above (it
+// never touches its last argument, LstmDirs), DR = true is nn.LSTM(I, H, 1, batch_first=True,
+// bidirectional=True): the grid's y index is a slot on the leading axis of every stacked array (whh
+// [D][4H][H], bih / bhh [D][4H], xproj / gates / dgates [D][B*T][4H], hprev / cst [D][B][T][H], h0 / c0 / hn /
+// cn / dh0 / dc0 [D][B][H]) and a column block of out / dout [B][T][D*H], which are written and read in place
+// through a row pitch.  The reverse direction is the same cell on mirrored time inside the clip's own length:
+//   per-clip families: step s of the walk works at time t = L - 1 - s, and "the row of step s - 1" is t + 1
+//     instead of t - 1 -- nothing else differs, so the state enters at t = L - 1, hprev[L - 1] is h0, hn / cn
+//     are the state after time 0 and dh0 / dc0 are the carries after the backward's last step, by the same code;
+//   per-step family: launch s works at time s in the forward direction and T - 1 - s in the reverse one (the
+//     direction is workgroup-uniform), so a pass stays T launches.  A reverse clip is dead FIRST in the forward
+//     pass (t >= L: zero out / hprev) and starts at its own t = L - 1: where the forward direction's "t = 0"
+//     is launch-uniform, "takes the state (or zero) as h_{prev}" is a per-clip select in the staging loop and
+//     the cell.  Its backward walks time upwards: dhn / dcn enter at t = 0, the recurrent sum reads dgates of
+//     row t - 1, c_{prev} is cst[t + 1] (c0 at L - 1), the clip goes dead at the END (zero dgates, carry
+//     left alone), and the dh0 launch sums over each clip's own row L_b - 1.
+// Direction 0 through the DR kernels is bit-identical to the kernels above, the reverse direction to the forward
+// one on input mirrored inside each length (tests/test_gpu_lstm_bidir.py).  Never a kernel that polls.
 #include "common.h"
 #include <stdlib.h>
 #include <mutex>
@@ -68,17 +87,24 @@ XCP_DEV float one_minus_sq_unfused(float v) {
 
 XCP_DEV int lstm_len(const int* __restrict__ lens, int b, int T) { return min(max(lens[b], 0), T); }
 
+// Direction-aware call (template parameter DR of the generic, register-resident and per-step kernels; see
+// "Directions" in the header comment).  The grid's y index is the slot on the stacked arrays' leading axis.
+struct LstmDirs {
+  int rev0;   // 1: slot 0 is the reverse direction (dirs = 2); slot 1 always is
+  int op;     // row pitch of out / dout in floats (D * H); slot di starts at column di * H
+};
+
 // xproj [B][T][4H] (already x W_ih^T); whhT [H][4H]; bias = b_ih + b_hh added here.
 // Outputs: out/h [B][T][H], hprev [B][T][H] (h_{t-1}), c [B][T][H],
 // gates [B][T][4H] post-activation (i, f, g, o), h_n / c_n [B][H].
-template <bool VL, bool ST>
+template <bool VL, bool ST, bool DR = false>
 __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__ xproj, const float* __restrict__ whhT,
                                                        const float* __restrict__ bih, const float* __restrict__ bhh,
                                                        float* __restrict__ out, float* __restrict__ hprev,
                                                        float* __restrict__ cst, float* __restrict__ gates,
                                                        float* __restrict__ hn, float* __restrict__ cn, int T, int H,
                                                        const int* __restrict__ lens, const float* __restrict__ h0,
-                                                       const float* __restrict__ c0) {
+                                                       const float* __restrict__ c0, LstmDirs dd) {
   extern __shared__ float sm[];   // h [H], c [H], gate pre-activations [4H]
   float* sh = sm;
   float* sc = sm + H;
@@ -86,13 +112,25 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
   const int b = blockIdx.x, tid = threadIdx.x;
   const int G4 = 4 * H;
   const int L = VL ? lstm_len(lens, b, T) : T;
+  bool rev = false;   // workgroup-uniform
+  int OP = H;
+  if constexpr (DR) {
+    const long di = blockIdx.y, nb = gridDim.x;
+    rev = (dd.rev0 | (int)di) != 0;
+    OP = dd.op;
+    xproj += di * nb * T * G4; whhT += di * H * G4; bih += di * G4; bhh += di * G4;
+    out += di * H; hprev += di * nb * T * H; cst += di * nb * T * H; gates += di * nb * T * G4;
+    hn += di * nb * H; cn += di * nb * H;
+    if constexpr (ST) { h0 += di * nb * H; c0 += di * nb * H; }
+  }
   if constexpr (ST) {   // h_{-1}, c_{-1}: step 0 saves h0 as its hprev, and L = 0 hands both on as h_n / c_n
     for (int k = tid; k < H; k += blockDim.x) { sh[k] = h0[(long)b * H + k]; sc[k] = c0[(long)b * H + k]; }
   } else {
     for (int k = tid; k < H; k += blockDim.x) { sh[k] = 0.f; sc[k] = 0.f; }
   }
   __syncthreads();
-  for (int t = 0; t < L; ++t) {
+  for (int s = 0; s < L; ++s) {
+    const int t = DR && rev ? L - 1 - s : s;   // the reverse direction visits L - 1 .. 0
     const float* xp = xproj + ((long)b * T + t) * G4;
     for (int j = tid; j < G4; j += blockDim.x) {
       float acc = xp[j] + bih[j] + bhh[j];
@@ -102,6 +140,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
     __syncthreads();
     float* gt = gates + ((long)b * T + t) * G4;
     const long ob = ((long)b * T + t) * H;
+    const long oo = DR ? ((long)b * T + t) * OP : ob;
     for (int k = tid; k < H; k += blockDim.x) {
       const float ig = sigm(sg[k]), fg = sigm(sg[H + k]), gg = tanhf(sg[2 * H + k]), og = sigm(sg[3 * H + k]);
       const float c = fmaf(fg, sc[k], ig * gg);
@@ -109,11 +148,11 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
       gt[k] = ig; gt[H + k] = fg; gt[2 * H + k] = gg; gt[3 * H + k] = og;
       hprev[ob + k] = sh[k];
       cst[ob + k] = c;
-      out[ob + k] = h;
+      out[oo + k] = h;
     }
     __syncthreads();
     for (int k = tid; k < H; k += blockDim.x) {
-      sh[k] = out[ob + k];
+      sh[k] = out[oo + k];
       sc[k] = cst[ob + k];
     }
     __syncthreads();
@@ -125,7 +164,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
   if constexpr (VL) {   // tail rows t >= L (contiguous): out and hprev zero (H is arbitrary here: 4-B stores)
     const long tb = ((long)b * T + L) * H, tn = (long)(T - L) * H;
     for (long e = tid; e < tn; e += blockDim.x) {
-      out[tb + e] = 0.f;
+      if constexpr (DR) out[((long)b * T + L + e / H) * OP + e % H] = 0.f;
+      else out[tb + e] = 0.f;
       hprev[tb + e] = 0.f;
     }
   }
@@ -134,13 +174,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const float* __restrict__
 // Backward through time.  dout [B][T][H] (may be null = zeros), dhn/dcn [B][H]
 // (may be null).  whh [4H][H] (row-major, as stored by nn.LSTM).
 // Writes dgates [B][T][4H] (pre-activation gradients).
-template <bool VL, bool ST>
+template <bool VL, bool ST, bool DR = false>
 __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ dhn,
                                                        const float* __restrict__ dcn, const float* __restrict__ whh,
                                                        const float* __restrict__ cst, const float* __restrict__ gates,
                                                        float* __restrict__ dgates, int T, int H,
                                                        const int* __restrict__ lens, const float* __restrict__ c0,
-                                                       float* __restrict__ dh0, float* __restrict__ dc0) {
+                                                       float* __restrict__ dh0, float* __restrict__ dc0, LstmDirs dd) {
   extern __shared__ float sm[];   // dh [H], dc [H], dgates_t [4H]
   float* sdh = sm;
   float* sdc = sm + H;
@@ -148,21 +188,39 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
   const int b = blockIdx.x, tid = threadIdx.x;
   const int G4 = 4 * H;
   const int L = VL ? lstm_len(lens, b, T) : T;
+  bool rev = false;   // workgroup-uniform
+  int OP = H;
+  if constexpr (DR) {
+    const long di = blockIdx.y, nb = gridDim.x;
+    rev = (dd.rev0 | (int)di) != 0;
+    OP = dd.op;
+    if (dout) dout += di * H;
+    if (dhn) dhn += di * nb * H;
+    if (dcn) dcn += di * nb * H;
+    whh += di * G4 * H; cst += di * nb * T * H; gates += di * nb * T * G4; dgates += di * nb * T * G4;
+    if constexpr (ST) {
+      if (c0) c0 += di * nb * H;
+      if (dh0) dh0 += di * nb * H;
+      if (dc0) dc0 += di * nb * H;
+    }
+  }
   for (int k = tid; k < H; k += blockDim.x) {
     sdh[k] = dhn ? dhn[(long)b * H + k] : 0.f;
     sdc[k] = dcn ? dcn[(long)b * H + k] : 0.f;
   }
   __syncthreads();
-  for (int t = L - 1; t >= 0; --t) {
+  for (int s = L - 1; s >= 0; --s) {   // s: the forward pass's step; time t is mirrored for the reverse direction
+    const int t = DR && rev ? L - 1 - s : s;
     const long ob = ((long)b * T + t) * H;
+    const long oo = DR ? ((long)b * T + t) * OP : ob;
     const float* gt = gates + ((long)b * T + t) * G4;
     float* dg = dgates + ((long)b * T + t) * G4;
     for (int k = tid; k < H; k += blockDim.x) {
-      const float dh = sdh[k] + (dout ? dout[ob + k] : 0.f);
+      const float dh = sdh[k] + (dout ? dout[oo + k] : 0.f);
       const float c = cst[ob + k];
-      float cp = 0.f;
-      if constexpr (ST) cp = t > 0 ? cst[ob - H + k] : (c0 ? c0[(long)b * H + k] : 0.f);
-      else cp = t > 0 ? cst[ob - H + k] : 0.f;
+      float cp = 0.f;   // c of step s - 1: the row before, or for the reverse direction the row after
+      if constexpr (ST) cp = s > 0 ? cst[(DR && rev ? ob + H : ob - H) + k] : (c0 ? c0[(long)b * H + k] : 0.f);
+      else cp = s > 0 ? cst[(DR && rev ? ob + H : ob - H) + k] : 0.f;
       const float ig = gt[k], fg = gt[H + k], gg = gt[2 * H + k], og = gt[3 * H + k];
       const float tc = tanhf(c);
       const float dO = dh * tc;
@@ -204,7 +262,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
 // except the per-step x-projection / state rows, which are prefetched one step ahead.
 //
 // forward: thread (gate j, part s), tid = j*S + s, holds W_hh[j][s*KPT .. +KPT).
-template <int H, bool VL, bool ST>
+template <int H, bool VL, bool ST, bool DR = false>
 __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restrict__ xproj,
                                                             const float* __restrict__ whh,
                                                             const float* __restrict__ bih,
@@ -214,13 +272,26 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
                                                             float* __restrict__ cn, int T,
                                                             const int* __restrict__ lens,
                                                             const float* __restrict__ h0,
-                                                            const float* __restrict__ c0) {
+                                                            const float* __restrict__ c0, LstmDirs dd) {
   constexpr int G4 = 4 * H, S = 1024 / G4, KPT = H / S, PADK = KPT + 4;
   static_assert(S >= 1 && KPT % 4 == 0, "unsupported H");
   __shared__ __attribute__((aligned(16))) float sh[S * PADK];   // h_{t-1}, part s at s*PADK (bank-spread)
   __shared__ float sg[G4];                                      // activated gates of step t
   const int tid = threadIdx.x, b = blockIdx.x;
   const int L = VL ? lstm_len(lens, b, T) : T;   // workgroup-uniform
+  bool rev = false;                              // workgroup-uniform
+  int OP = H;
+  if constexpr (DR) {
+    const long di = blockIdx.y, nb = gridDim.x;
+    rev = (dd.rev0 | (int)di) != 0;
+    OP = dd.op;
+    xproj += di * nb * T * G4; whh += di * G4 * H; bih += di * G4; bhh += di * G4;
+    out += di * H; hprev += di * nb * T * H; cst += di * nb * T * H; gates += di * nb * T * G4;
+    hn += di * nb * H; cn += di * nb * H;
+    if constexpr (ST) { h0 += di * nb * H; c0 += di * nb * H; }
+  }
+  // time of step q: the reverse direction visits L - 1 .. 0
+  auto tof = [&](int q) { return DR && rev ? L - 1 - q : q; };
   const int j = tid / S, s = tid % S;
   float w[KPT];
   const float* wp = whh + (long)j * H + s * KPT;
@@ -242,11 +313,12 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
     if (tid < H) sh[hidx(tid)] = 0.f;
   }
   const float* xb = xproj + (long)b * T * G4;
-  float xn = s == 0 ? xb[j] : 0.f;               // (row 0 exists for L = 0 too: T >= 1)
+  float xn = s == 0 ? xb[(long)(DR ? max(tof(0), 0) : 0) * G4 + j] : 0.f;   // (row 0 exists for L = 0 too: T >= 1)
   __syncthreads();
-  for (int t = 0; t < L; ++t) {
+  for (int q = 0; q < L; ++q) {
+    const int t = tof(q);
     const float xc = xn;
-    if (s == 0 && t + 1 < L) xn = xb[(long)(t + 1) * G4 + j];
+    if (s == 0 && q + 1 < L) xn = xb[(long)tof(q + 1) * G4 + j];
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     const float* hp = sh + s * PADK;
 #pragma unroll
@@ -274,7 +346,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
       c = fmaf(fg, c, ig * gg);
       const float h = og * tanhf(c);
       cst[ob] = c;
-      out[ob] = h;
+      out[DR ? ((long)b * T + t) * OP + tid : ob] = h;
       sh[hidx(tid)] = h;      // every read of h_{t-1} happened before the barrier above
     }
     __syncthreads();
@@ -291,7 +363,8 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
     float4* ph = reinterpret_cast<float4*>(hprev + ((long)b * T + L) * H);
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     for (long e = tid; e < n4; e += 1024) {
-      po[e] = z;
+      if constexpr (DR) *reinterpret_cast<float4*>(out + ((long)b * T + L + e / (H / 4)) * OP + e % (H / 4) * 4) = z;
+      else po[e] = z;
       ph[e] = z;
     }
   }
@@ -300,7 +373,7 @@ __global__ __launch_bounds__(1024) void lstm_fwd_reg_kernel(const float* __restr
 // backward: thread (unit k, part p), tid = k*P + p, holds W_hh[p*JPT .. +JPT)[k]; the
 // step's pre-activation gradients are broadcast from LDS and dh_{t-1}[k] is reduced over
 // the P parts (adjacent lanes) by shuffles.
-template <int H, bool VL, bool ST>
+template <int H, bool VL, bool ST, bool DR = false>
 __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restrict__ dout,
                                                             const float* __restrict__ dhn,
                                                             const float* __restrict__ dcn,
@@ -310,13 +383,30 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
                                                             float* __restrict__ dgates, int T,
                                                             const int* __restrict__ lens,
                                                             const float* __restrict__ c0,
-                                                            float* __restrict__ dh0, float* __restrict__ dc0) {
+                                                            float* __restrict__ dh0, float* __restrict__ dc0,
+                                                            LstmDirs dd) {
   constexpr int G4 = 4 * H, P = 1024 / H, JPT = G4 / P, PADJ = JPT + 4;
   static_assert(P >= 1 && JPT % 4 == 0, "unsupported H");
   __shared__ __attribute__((aligned(16))) float sdg[P * PADJ];
   __shared__ float sdh[H];
   const int tid = threadIdx.x, b = blockIdx.x;
   const int L = VL ? lstm_len(lens, b, T) : T;   // workgroup-uniform
+  bool rev = false;                              // workgroup-uniform
+  int OP = H;
+  if constexpr (DR) {
+    const long di = blockIdx.y, nb = gridDim.x;
+    rev = (dd.rev0 | (int)di) != 0;
+    OP = dd.op;
+    if (dout) dout += di * H;
+    if (dhn) dhn += di * nb * H;
+    if (dcn) dcn += di * nb * H;
+    whh += di * G4 * H; cst += di * nb * T * H; gates += di * nb * T * G4; dgates += di * nb * T * G4;
+    if constexpr (ST) {
+      if (c0) c0 += di * nb * H;
+      if (dh0) dh0 += di * nb * H;
+      if (dc0) dc0 += di * nb * H;
+    }
+  }
   const int k = tid / P, p = tid % P;
   float w[JPT];
 #pragma unroll
@@ -325,14 +415,15 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
   float dc = 0.f;                                // dc carried into step t, unit tid < H
   // per-step inputs of unit tid, prefetched one step ahead
   float n_c = 0.f, n_cp = 0.f, n_i = 0.f, n_f = 0.f, n_g = 0.f, n_o = 0.f, n_do = 0.f;
-  auto fetch = [&](int t) {
+  auto fetch = [&](int q) {   // q: the forward pass's step; its time is mirrored for the reverse direction
+    const int t = DR && rev ? L - 1 - q : q;
     const long ob = ((long)b * T + t) * H + tid;
     const float* gt = gates + ((long)b * T + t) * G4;
-    n_c = cst[ob];
-    if constexpr (ST) n_cp = t > 0 ? cst[ob - H] : (c0 ? c0[(long)b * H + tid] : 0.f);
-    else n_cp = t > 0 ? cst[ob - H] : 0.f;
+    n_c = cst[ob];   // (c of step q - 1: the row before, or for the reverse direction the row after)
+    if constexpr (ST) n_cp = q > 0 ? cst[DR && rev ? ob + H : ob - H] : (c0 ? c0[(long)b * H + tid] : 0.f);
+    else n_cp = q > 0 ? cst[DR && rev ? ob + H : ob - H] : 0.f;
     n_i = gt[tid]; n_f = gt[H + tid]; n_g = gt[2 * H + tid]; n_o = gt[3 * H + tid];
-    n_do = dout ? dout[ob] : 0.f;
+    n_do = dout ? dout[DR ? ((long)b * T + t) * OP + tid : ob] : 0.f;
   };
   if (tid < H) {
     sdh[tid] = dhn ? dhn[(long)b * H + tid] : 0.f;
@@ -340,11 +431,12 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
     if (!VL || L > 0) fetch(L - 1);
   }
   __syncthreads();
-  for (int t = L - 1; t >= 0; --t) {
+  for (int q = L - 1; q >= 0; --q) {
+    const int t = DR && rev ? L - 1 - q : q;
     if (tid < H) {
       const float c = n_c, cp = n_cp, ig = n_i, fg = n_f, gg = n_g, og = n_o;
       const float dh = sdh[tid] + n_do;
-      if (t > 0) fetch(t - 1);
+      if (q > 0) fetch(q - 1);
       const float tc = tanhf(c);
       const float dO = dh * tc;
       const float dct = dc + dh * og * (1.f - tc * tc);
@@ -407,20 +499,36 @@ __global__ __launch_bounds__(1024) void lstm_bwd_reg_kernel(const float* __restr
 constexpr int LS_UPW = 2;              // hidden units per workgroup
 constexpr int LS_MAXB = 32;            // clips (register partials per thread)
 
-template <int KS, bool VL, bool ST>   // KS = H / 32 (k values per slice)
+template <int KS, bool VL, bool ST, bool DR = false>   // KS = H / 32 (k values per slice)
 __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restrict__ xproj, const float* __restrict__ whh,
                                                             const float* __restrict__ bih, const float* __restrict__ bhh,
                                                             float* __restrict__ out, float* __restrict__ hprev,
                                                             float* __restrict__ cst, float* __restrict__ gates,
                                                             float* __restrict__ hn, float* __restrict__ cn, int B, int T,
                                                             int t, const int* __restrict__ lens,
-                                                            const float* __restrict__ h0, const float* __restrict__ c0) {
+                                                            const float* __restrict__ h0, const float* __restrict__ c0,
+                                                            LstmDirs dd) {
   constexpr int H = KS * 32, G4 = 4 * H, PS = KS + 4;   // LDS slice pitch (floats)
   constexpr int RP = 33;                                // pitch of a (row, clip) partial row
   extern __shared__ float sm[];   // h_{t-1} [B][32][PS] (then the partials [8][B][RP]), then pre [8][B]
   float* sh = sm;
   float* spre = sm + B * 32 * PS;
   const int tid = threadIdx.x, u0 = blockIdx.x * LS_UPW;
+  // DR: launch s (the argument t) is time s for the forward direction and time T - 1 - s for the reverse
+  // one, whose "previous" row is t + 1; a clip of the reverse direction starts (takes the state, or zero) at
+  // its own t = L - 1, a per-clip condition where the forward direction's t = 0 is launch-uniform
+  bool rev = false;   // workgroup-uniform
+  int OP = H;
+  if constexpr (DR) {
+    const long di = blockIdx.y;
+    rev = (dd.rev0 | (int)di) != 0;
+    OP = dd.op;
+    if (rev) t = T - 1 - t;
+    xproj += di * B * T * G4; whh += di * G4 * H; bih += di * G4; bhh += di * G4;
+    out += di * H; hprev += di * B * T * H; cst += di * B * T * H; gates += di * B * T * G4;
+    hn += di * B * H; cn += di * B * H;
+    if constexpr (ST) { h0 += di * B * H; c0 += di * B * H; }
+  }
   const int r = tid >> 5, s = tid & 31, q = r >> 1, uu = r & 1;
   const int j = q * H + u0 + uu;
   // W_hh row slice
@@ -437,21 +545,34 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
   const int tp = t > 0 ? t - 1 : 0;
   for (int e0 = tid; e0 < n4; e0 += 8 * 256) {
     float4 v[8];
+    [[maybe_unused]] bool fst[8];   // DR: the clip starts at this step (its h_{t-1} is the state, or zero)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int e = min(e0 + i * 256, n4 - 1);
       const int b = e / (H / 4), k4 = (e - b * (H / 4)) * 4;
-      const float* src = out + ((long)b * T + tp) * H + k4;
-      if constexpr (ST) src = t > 0 ? src : h0 + (long)b * H + k4;
-      v[i] = *reinterpret_cast<const float4*>(src);
+      if constexpr (DR) {
+        // reverse: row t + 1 (clamped), and the state at t >= L_b - 1 (a clip past its end stages the state or
+        // zero: finite, and nothing of it is used)
+        fst[i] = rev ? t + 1 >= (VL ? lstm_len(lens, b, T) : T) : t == 0;
+        const int rp = rev ? min(t + 1, T - 1) : tp;
+        const float* src = out + ((long)b * T + rp) * OP + k4;
+        if constexpr (ST) src = fst[i] ? h0 + (long)b * H + k4 : src;
+        v[i] = *reinterpret_cast<const float4*>(src);
+      } else {
+        const float* src = out + ((long)b * T + tp) * H + k4;
+        if constexpr (ST) src = t > 0 ? src : h0 + (long)b * H + k4;
+        v[i] = *reinterpret_cast<const float4*>(src);
+      }
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int e = e0 + i * 256;
       const int b = e / (H / 4), k4 = (e - b * (H / 4)) * 4;
+      bool keep = ST || t > 0;
+      if constexpr (DR) keep = ST || !fst[i];
       if (e < n4)
         *reinterpret_cast<float4*>(sh + (b * 32 + k4 / KS) * PS + (k4 % KS)) =
-            ST || t > 0 ? v[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            keep ? v[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   __syncthreads();
@@ -510,24 +631,33 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
     }
     const float ig = sigm(pre[0]), fg = sigm(pre[1]), gg = tanhf(pre[2]), og = sigm(pre[3]);
     const long ob = ((long)b * T + t) * H;
+    const long oo = DR ? ((long)b * T + t) * OP : ob;
     const long op = t > 0 ? ob - H + k : ob + k;   // t = 0: a valid stand-in, selected away
     // (t > L: row t - 1 of cst was never written -- a valid address whose value is selected away)
     const float* pcp = cst + op;
     const float* php = out + op;
-    if constexpr (ST) {   // t = 0: the state itself
-      pcp = t > 0 ? pcp : c0 + (long)b * H + k;
-      php = t > 0 ? php : h0 + (long)b * H + k;
+    // the clip has a previous step; reverse direction: not at t = L - 1, nor at any t past the end
+    bool hasp = t > 0;
+    if constexpr (DR) {
+      if (rev) hasp = t + 1 < L;
+      const long dp = !hasp ? 0 : (rev ? 1 : -1);   // no previous step: its own row, a valid stand-in, selected away
+      pcp = cst + ob + dp * H + k;
+      php = out + oo + dp * OP + k;
+    }
+    if constexpr (ST) {   // no previous step: the state itself
+      pcp = hasp ? pcp : c0 + (long)b * H + k;
+      php = hasp ? php : h0 + (long)b * H + k;
     }
     const float vcp = *pcp, vhp = *php;
-    const float cp = ST || t > 0 ? vcp : 0.f;
+    const float cp = ST || hasp ? vcp : 0.f;
     const float c = fmaf(fg, cp, ig * gg);
     const float h = og * tanhf(c);
     float* gt = gates + ((long)b * T + t) * G4;
     if (live) { gt[k] = ig; gt[H + k] = fg; gt[2 * H + k] = gg; gt[3 * H + k] = og; }
-    hprev[ob + k] = live && (ST || t > 0) ? vhp : 0.f;
+    hprev[ob + k] = live && (ST || hasp) ? vhp : 0.f;
     if (live) cst[ob + k] = c;
-    out[ob + k] = live ? h : 0.f;
-    if (t == L - 1) {
+    out[oo + k] = live ? h : 0.f;
+    if (DR && rev ? t == 0 && L > 0 : t == L - 1) {   // the clip's last step
       hn[(long)b * H + k] = h;
       cn[(long)b * H + k] = c;
     }
@@ -557,14 +687,18 @@ __global__ __launch_bounds__(256) void lstm_transpose_kernel(const float* __rest
 // With lengths, clip b at t >= L writes zero dgates (so the recurrent sum into its step L - 1
 // vanishes on its own) and leaves its carry alone; at t = L - 1 it takes dhn / dcn as a full clip
 // does at T - 1.
-template <bool VL, bool ST>
+// DR: launch t (T - 1 .. 0, then -1 for dh0) is time t for the forward direction and time T - 1 - t for the
+// reverse one, which therefore walks 0 .. T - 1: its recurrent sum reads dgates of row time - 1, it takes
+// dhn / dcn at time 0, its c_{prev} is cst[time + 1] (c0 at L - 1), its clips go dead at the END of the walk
+// (time >= L: zero dgates, carry left alone), and the dh0 launch sums over row L_b - 1 of each clip.
+template <bool VL, bool ST, bool DR = false>
 __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restrict__ dout, const float* __restrict__ dhn,
                                                             const float* __restrict__ dcn, const float* __restrict__ whhT,
                                                             const float* __restrict__ cst, const float* __restrict__ gates,
                                                             float* __restrict__ dgates, float* __restrict__ dcw, int B,
                                                             int T, int H, int t, const int* __restrict__ lens,
                                                             const float* __restrict__ c0, float* __restrict__ dh0,
-                                                            float* __restrict__ dc0) {
+                                                            float* __restrict__ dc0, LstmDirs dd) {
   extern __shared__ float sm[];   // W columns [16 slices][SP] ([4H / 16][2] each), dh [B][2]
   const int G4 = 4 * H;
   const int per = G4 / 16, SP = 2 * per + 4;   // slice pitch: +4 floats, so the 16 slices of a
@@ -572,7 +706,24 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
   float* swc = sm;
   float* sdh = sm + 16 * SP;
   const int tid = threadIdx.x, u0 = blockIdx.x * LS_UPW;
-  if (t < T - 1) {
+  bool rev = false;   // workgroup-uniform
+  int OP = H;
+  if constexpr (DR) {
+    const long di = blockIdx.y;
+    rev = (dd.rev0 | (int)di) != 0;
+    OP = dd.op;
+    if (dout) dout += di * H;
+    if (dhn) dhn += di * B * H;
+    if (dcn) dcn += di * B * H;
+    whhT += di * ((long)B * H + (long)G4 * H); dcw += di * ((long)B * H + (long)G4 * H);   // work: [D][carry, W_hh^T]
+    cst += di * B * T * H; gates += di * B * T * G4; dgates += di * B * T * G4;
+    if constexpr (ST) {
+      if (c0) c0 += di * B * H;
+      if (dh0) dh0 += di * B * H;
+      if (dc0) dc0 += di * B * H;
+    }
+  }
+  if (t < T - 1) {   // (the launch index: every launch but the first has a recurrent sum, in either direction)
     // rows u0, u0+1 of W_hh^T (contiguous), interleaved into swc[j][2]: 16-B loads, up to 4 per
     // row per thread issued before any store (clamped indices; a loop of dependent scalar loads
     // was ~8 L2 round trips a step at H = 512)
@@ -602,7 +753,15 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
       const int b = b0 + (tid >> 4), sl = tid & 15;
       float a0 = 0.f, a1 = 0.f;
       if (b < B) {
-        const float* dg = dgates + ((long)b * T + t + 1) * G4 + sl * per;
+        const float* dg = dgates + ((long)b * T + t + 1) * G4 + sl * per;   // the row the previous launch wrote
+        if constexpr (DR) {
+          if (rev) {
+            int rr = T - 2 - t;
+            if constexpr (VL && ST)   // reverse dh0 launch: each clip's last live step is its own L_b - 1
+              if (t < 0) rr = max(lstm_len(lens, b, T) - 1, 0);
+            dg = dgates + ((long)b * T + rr) * G4 + sl * per;
+          }
+        }
         const float* wc = swc + sl * SP;
         // 16 independent 16-B loads in flight per batch (the loop is L2-latency-bound otherwise)
         for (int i0 = 0; i0 < per; i0 += 64) {
@@ -649,27 +808,42 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(const float* __restr
         return;
       }
     }
+    if constexpr (DR) {
+      if (rev) t = T - 1 - t;   // the time this launch works at
+    }
     const bool live = !VL || t < L;
     const long ob = ((long)b * T + t) * H, bk = (long)b * H + k;
     // every global load unconditional (absent operands, and every operand of a clip past its end,
     // read a valid stand-in address and are selected away), so they go out together instead of one
     // round trip per branch
-    const bool last = t == L - 1;
+    bool last = t == L - 1;   // the step the backward enters at: takes dhn / dcn
+    if constexpr (DR) {
+      if (rev) last = t == 0;
+    }
     const float* pc = cst + ob + k;
     const float vhn = *(last && dhn ? dhn + bk : pc);
     const float vcw = *(!last ? dcw + bk : (dcn ? dcn + bk : pc));
-    const float vdo = *(dout ? dout + ob + k : pc);
-    const float* pcp = t > 0 ? pc - H : pc;
-    if constexpr (ST) pcp = t > 0 || !c0 ? pcp : c0 + bk;
+    const float* pdo = dout + ob + k;
+    if constexpr (DR) pdo = dout + ((long)b * T + t) * OP + k;
+    const float vdo = *(dout ? pdo : pc);
+    bool hasp = t > 0;        // the forward pass had a step before this one
+    const float* pcp = hasp ? pc - H : pc;
+    if constexpr (DR) {
+      if (rev) {
+        hasp = t + 1 < L;
+        pcp = hasp ? pc + H : pc;
+      }
+    }
+    if constexpr (ST) pcp = hasp || !c0 ? pcp : c0 + bk;
     const float vcp = *pcp;
     const float c = *pc;
     const float* gt = gates + ((long)b * T + t) * G4;
     const float ig = gt[k], fg = gt[H + k], gg = gt[2 * H + k], og = gt[3 * H + k];
-    // (t < T - 1 whenever !last && live, so sdh was written above)
+    // (not the first launch whenever !last && live, so sdh was written above)
     const float dhr = !last ? sdh[b * 2 + v] : (dhn ? vhn : 0.f);
     const float dcr = !last || dcn ? vcw : 0.f;
     const float dh = dhr + (dout ? vdo : 0.f);
-    const float cp = t > 0 || (ST && c0) ? vcp : 0.f;
+    const float cp = hasp || (ST && c0) ? vcp : 0.f;
     const float tc = tanhf(c);
     const float dO = dh * tc;
     // dcr + dh * og * (1 - tc * tc) with its roundings spelled out: left to the compiler, one
@@ -1350,10 +1524,10 @@ int lstm_fwd_launch(const float* xproj, const float* whh, const float* whhT, con
   if (lstm_reg(H, kernel)) {
     if (H == 128)
       hipLaunchKernelGGL((lstm_fwd_reg_kernel<128, VL, ST>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out,
-                         hprev, cst, gates, hn, cn, T, lens, h0, c0);
+                         hprev, cst, gates, hn, cn, T, lens, h0, c0, LstmDirs{});
     else
       hipLaunchKernelGGL((lstm_fwd_reg_kernel<64, VL, ST>), dim3(B), dim3(1024), 0, st, xproj, whh, bih, bhh, out,
-                         hprev, cst, gates, hn, cn, T, lens, h0, c0);
+                         hprev, cst, gates, hn, cn, T, lens, h0, c0, LstmDirs{});
     return (int)hipGetLastError();
   }
   if (lstm_step(B, H, kernel)) {
@@ -1361,20 +1535,20 @@ int lstm_fwd_launch(const float* xproj, const float* whh, const float* whhT, con
     for (int t = 0; t < T; ++t) {
       if (H == 256)
         hipLaunchKernelGGL((lstm_fwd_step_kernel<8, VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih,
-                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0);
+                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0, LstmDirs{});
       else if (H == 512)
         hipLaunchKernelGGL((lstm_fwd_step_kernel<16, VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih,
-                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0);
+                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0, LstmDirs{});
       else
         hipLaunchKernelGGL((lstm_fwd_step_kernel<32, VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, xproj, whh, bih,
-                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0);
+                           bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0, LstmDirs{});
     }
     return (int)hipGetLastError();
   }
   if (!whhT) return XCP_EINVAL;
   const size_t smem = (size_t)6 * H * sizeof(float);
   hipLaunchKernelGGL((lstm_fwd_kernel<VL, ST>), dim3(B), dim3(256), smem, st, xproj, whhT, bih, bhh, out, hprev, cst,
-                     gates, hn, cn, T, H, lens, h0, c0);
+                     gates, hn, cn, T, H, lens, h0, c0, LstmDirs{});
   return (int)hipGetLastError();
 }
 
@@ -1419,21 +1593,21 @@ int lstm_bwd_launch(const float* dout, const float* dhn, const float* dcn, const
     const size_t smem = ((size_t)8 * H + 64 + 2 * B) * sizeof(float);
     for (int t = T - 1; t >= (ST && (dh0 || dc0) ? -1 : 0); --t)
       hipLaunchKernelGGL((lstm_bwd_step_kernel<VL, ST>), dim3(H / LS_UPW), dim3(256), smem, st, dout, dhn, dcn, whhT, cst,
-                         gates, dgates, work, B, T, H, t, lens, c0, dh0, dc0);
+                         gates, dgates, work, B, T, H, t, lens, c0, dh0, dc0, LstmDirs{});
     return (int)hipGetLastError();
   }
   if (lstm_reg(H, kernel)) {
     if (H == 128)
       hipLaunchKernelGGL((lstm_bwd_reg_kernel<128, VL, ST>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
-                         dgates, T, lens, c0, dh0, dc0);
+                         dgates, T, lens, c0, dh0, dc0, LstmDirs{});
     else
       hipLaunchKernelGGL((lstm_bwd_reg_kernel<64, VL, ST>), dim3(B), dim3(1024), 0, st, dout, dhn, dcn, whh, cst, gates,
-                         dgates, T, lens, c0, dh0, dc0);
+                         dgates, T, lens, c0, dh0, dc0, LstmDirs{});
     return (int)hipGetLastError();
   }
   const size_t smem = (size_t)6 * H * sizeof(float);
   hipLaunchKernelGGL((lstm_bwd_kernel<VL, ST>), dim3(B), dim3(256), smem, st, dout, dhn, dcn, whh, cst, gates, dgates, T,
-                     H, lens, c0, dh0, dc0);
+                     H, lens, c0, dh0, dc0, LstmDirs{});
   return (int)hipGetLastError();
 }
 
@@ -1494,6 +1668,79 @@ int lstm_bwd(const float* dout, const float* dhn, const float* dcn, const float*
   }
   return lens ? lstm_bwd_launch<true>(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st)
               : lstm_bwd_launch<false>(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st);
+}
+
+// Direction-aware forward / backward (the DR instantiations): D = 1 (dirs 1 or 2) or 2 (dirs 3) slots of the
+// stacked arrays, both in the same launches -- grid (B, D) for the per-clip families, (H / 2, D) per step.
+template <bool VL, bool ST>
+int lstm_fwd_dir_launch(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh,
+                        const float* h0, const float* c0, float* out, float* hprev, float* cst, float* gates, float* hn,
+                        float* cn, const int* lens, int B, int T, int H, int kernel, int dirs, hipStream_t st) {
+  const int D = dirs == 3 ? 2 : 1;
+  const LstmDirs dd{dirs == 2 ? 1 : 0, D * H};
+  if (lstm_reg(H, kernel)) {
+    if (H == 128)
+      hipLaunchKernelGGL((lstm_fwd_reg_kernel<128, VL, ST, true>), dim3(B, D), dim3(1024), 0, st, xproj, whh, bih, bhh,
+                         out, hprev, cst, gates, hn, cn, T, lens, h0, c0, dd);
+    else
+      hipLaunchKernelGGL((lstm_fwd_reg_kernel<64, VL, ST, true>), dim3(B, D), dim3(1024), 0, st, xproj, whh, bih, bhh,
+                         out, hprev, cst, gates, hn, cn, T, lens, h0, c0, dd);
+    return (int)hipGetLastError();
+  }
+  if (lstm_step(B, H, kernel)) {
+    const size_t smem = ((size_t)B * 32 * (H / 32 + 4) + 8 * B) * sizeof(float);
+    for (int t = 0; t < T; ++t) {
+      if (H == 256)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<8, VL, ST, true>), dim3(H / LS_UPW, D), dim3(256), smem, st, xproj, whh,
+                           bih, bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0, dd);
+      else if (H == 512)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<16, VL, ST, true>), dim3(H / LS_UPW, D), dim3(256), smem, st, xproj, whh,
+                           bih, bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0, dd);
+      else
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<32, VL, ST, true>), dim3(H / LS_UPW, D), dim3(256), smem, st, xproj, whh,
+                           bih, bhh, out, hprev, cst, gates, hn, cn, B, T, t, lens, h0, c0, dd);
+    }
+    return (int)hipGetLastError();
+  }
+  if (!whhT) return XCP_EINVAL;
+  const size_t smem = (size_t)6 * H * sizeof(float);
+  hipLaunchKernelGGL((lstm_fwd_kernel<VL, ST, true>), dim3(B, D), dim3(256), smem, st, xproj, whhT, bih, bhh, out, hprev,
+                     cst, gates, hn, cn, T, H, lens, h0, c0, dd);
+  return (int)hipGetLastError();
+}
+
+// work (per-step kernels only): [D][cell-gradient carry B*H, W_hh^T H*4H]
+template <bool VL, bool ST>
+int lstm_bwd_dir_launch(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* c0,
+                        const float* cst, const float* gates, float* dgates, float* dh0, float* dc0, float* work,
+                        const int* lens, int B, int T, int H, int kernel, int dirs, hipStream_t st) {
+  const int D = dirs == 3 ? 2 : 1;
+  const LstmDirs dd{dirs == 2 ? 1 : 0, D * H};
+  if (lstm_step(B, H, kernel)) {
+    if (!work) return XCP_EINVAL;
+    const long ws = (long)B * H + (long)4 * H * H;
+    for (int d = 0; d < D; ++d)
+      hipLaunchKernelGGL(lstm_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, st, whh + (long)d * 4 * H * H,
+                         work + d * ws + (long)B * H, H);
+    const size_t smem = ((size_t)8 * H + 64 + 2 * B) * sizeof(float);
+    for (int t = T - 1; t >= (ST && (dh0 || dc0) ? -1 : 0); --t)
+      hipLaunchKernelGGL((lstm_bwd_step_kernel<VL, ST, true>), dim3(H / LS_UPW, D), dim3(256), smem, st, dout, dhn, dcn,
+                         work + (long)B * H, cst, gates, dgates, work, B, T, H, t, lens, c0, dh0, dc0, dd);
+    return (int)hipGetLastError();
+  }
+  if (lstm_reg(H, kernel)) {
+    if (H == 128)
+      hipLaunchKernelGGL((lstm_bwd_reg_kernel<128, VL, ST, true>), dim3(B, D), dim3(1024), 0, st, dout, dhn, dcn, whh, cst,
+                         gates, dgates, T, lens, c0, dh0, dc0, dd);
+    else
+      hipLaunchKernelGGL((lstm_bwd_reg_kernel<64, VL, ST, true>), dim3(B, D), dim3(1024), 0, st, dout, dhn, dcn, whh, cst,
+                         gates, dgates, T, lens, c0, dh0, dc0, dd);
+    return (int)hipGetLastError();
+  }
+  const size_t smem = (size_t)6 * H * sizeof(float);
+  hipLaunchKernelGGL((lstm_bwd_kernel<VL, ST, true>), dim3(B, D), dim3(256), smem, st, dout, dhn, dcn, whh, cst, gates,
+                     dgates, T, H, lens, c0, dh0, dc0, dd);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -1579,6 +1826,39 @@ int xcp_lstm_bwd_state(const float* dout, const float* dhn, const float* dcn, co
                                             dh0, dc0)
               : lstm_bwd_launch<false, true>(dout, dhn, dcn, whh, cst, gates, dgates, work, lens, B, T, H, kernel, st, c0,
                                              dh0, dc0);
+}
+
+// Both directions of time: nn.LSTM(I, H, 1, batch_first=True, bidirectional=True), with lengths (lens non-null)
+// over packed input.  dirs is a mask: 1 = the forward direction only, 2 = the reverse one only, 3 = both, with
+// D = 1, 1, 2 slots on the leading axis of every stacked array (whh [D][4H][H], whhT [D][H][4H], bih / bhh
+// [D][4H], xproj / gates / dgates [D][B*T][4H], hprev / cst [D][B][T][H], h0 / c0 / hn / cn / dh0 / dc0
+// [D][B][H]); out / dout are [B][T][D*H], slot d in columns d*H .. d*H + H.  h0 / c0 are nullable together,
+// lens is nullable, dh0 / dc0 each.  Runs the register-resident, per-step or generic kernels only -- never one
+// that polls -- and both directions in the same launches.  work: D * (B*H + 4*H*H) floats (per-step kernels).
+int xcp_lstm_dir_needs_whhT(int B, int H, int kernel) { return lstm_reg(H, kernel) || lstm_step(B, H, kernel) ? 0 : 1; }
+
+int xcp_lstm_fwd_dir(const float* xproj, const float* whh, const float* whhT, const float* bih, const float* bhh,
+                     const float* h0, const float* c0, float* out, float* hprev, float* cst, float* gates, float* hn,
+                     float* cn, const int* lens, int B, int T, int H, int kernel, int dirs, hipStream_t st) {
+  if ((h0 == nullptr) != (c0 == nullptr) || dirs < 1 || dirs > 3) return XCP_EINVAL;
+  if (B <= 0 || T <= 0) return XCP_OK;
+  if (H <= 0 || kernel < 0 || kernel > 1) return XCP_EINVAL;
+#define XCP_LFD(VL, ST) lstm_fwd_dir_launch<VL, ST>(xproj, whh, whhT, bih, bhh, h0, c0, out, hprev, cst, gates, hn, cn, lens, B, T, H, kernel, dirs, st)
+  if (h0) return lens ? XCP_LFD(true, true) : XCP_LFD(false, true);
+  return lens ? XCP_LFD(true, false) : XCP_LFD(false, false);
+#undef XCP_LFD
+}
+
+int xcp_lstm_bwd_dir(const float* dout, const float* dhn, const float* dcn, const float* whh, const float* c0,
+                     const float* cst, const float* gates, float* dgates, float* dh0, float* dc0, float* work,
+                     const int* lens, int B, int T, int H, int kernel, int dirs, hipStream_t st) {
+  if (dirs < 1 || dirs > 3) return XCP_EINVAL;
+  if (B <= 0 || T <= 0) return XCP_OK;
+  if (H <= 0 || kernel < 0 || kernel > 1) return XCP_EINVAL;
+#define XCP_LBD(VL, ST) lstm_bwd_dir_launch<VL, ST>(dout, dhn, dcn, whh, c0, cst, gates, dgates, dh0, dc0, work, lens, B, T, H, kernel, dirs, st)
+  if (c0 || dh0 || dc0) return lens ? XCP_LBD(true, true) : XCP_LBD(false, true);
+  return lens ? XCP_LBD(true, false) : XCP_LBD(false, false);
+#undef XCP_LBD
 }
 
 }  // extern "C"

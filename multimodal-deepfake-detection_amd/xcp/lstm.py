@@ -20,6 +20,10 @@ Zero-padded clips of unequal length (the loaders' ``seq_lengths``) go through
 An initial state ``hx = (h0, c0)`` goes through ``torch.ops.xcp.lstm_state`` (state-aware instantiations of
 the same kernels), with or without lengths: a long clip can be fed in chunks of frames with the state
 carried from one chunk to the next (xcp/streaming.py), and ``h0`` / ``c0`` are differentiable.
+
+``bidirectional=True`` goes through ``torch.ops.xcp.lstm_bidir``: direction-aware instantiations of the same
+kernels run the two directions of time in the same launches, the reverse one reading each clip backwards from
+its own last frame, and write ``out [B, T, 2H]`` in place.
 """
 import torch
 import torch.nn as nn
@@ -30,7 +34,7 @@ from . import torch_ops  # noqa: F401  (registers torch.ops.xcp.lstm, .lstm_varl
 
 class LSTM(nn.LSTM):
     """nn.LSTM with the xcp forward.  Supported configuration (the reference's):
-    num_layers=1, batch_first=True, unidirectional, bias=True, proj_size=0.
+    num_layers=1, batch_first=True, bias=True, proj_size=0, one or both directions of time.
     ``xcp_kernel`` (attribute): 0 = automatic recurrence kernel choice, 1 = the generic kernels.
 
     ``forward(input, hx=None, lengths=None)``: with ``lengths`` (int32 / int64 ``[B]``) clip ``b`` is
@@ -48,14 +52,21 @@ class LSTM(nn.LSTM):
     0 hands its state on unchanged (``h_n = h0``, ``c_n = c0``, ``d/dh0 = d/dh_n``, ``d/dc0 = d/dc_n``), which
     is what carries a short clip's state through the later chunks of a batch.  A call with ``hx`` runs the
     register-resident, per-step or generic kernels, never the persistent ones; ``hx=None`` calls exactly the
-    ops it always did."""
+    ops it always did.
+
+    ``bidirectional=True`` (parameters ``weight_ih_l0_reverse`` ... as ``nn.LSTM`` names and initialises them, so
+    its checkpoints load): returns ``(out [B, T, 2H], (h_n [2, B, H], c_n [2, B, H]))`` with the forward
+    direction in ``out[..., :H]`` / ``h_n[0]`` and the reverse one in ``out[..., H:]`` / ``h_n[1]``, the state
+    after the clip's first frame.  ``hx`` is ``[2, B, H]`` each; lengths, ``PackedSequence`` input and the
+    length-0 rule work as above, per direction.  It never runs the persistent kernels either.  ``num_layers``
+    stays 1: a deeper stack is a second ``LSTM(2 * H, H, bidirectional=True)`` module fed this one's ``out``."""
 
     xcp_kernel = 0
 
     def forward(self, input, hx=None, lengths=None):  # noqa: A002  (nn.LSTM signature)
-        if self.num_layers != 1 or not self.batch_first or self.bidirectional or not self.bias or self.proj_size:
+        if self.num_layers != 1 or not self.batch_first or not self.bias or self.proj_size:
             raise NotImplementedError("xcp LSTM supports the reference configuration only "
-                                      "(1 layer, batch_first, unidirectional, bias, no projection)")
+                                      "(1 layer, batch_first, bias, no projection)")
         if isinstance(input, PackedSequence):
             if lengths is not None:
                 raise ValueError("a PackedSequence carries its own lengths; do not pass lengths= with it")
@@ -68,6 +79,15 @@ class LSTM(nn.LSTM):
             h0, c0 = self._check_hx(hx, input)
         if not input.is_cuda:
             raise RuntimeError("xcp LSTM runs on the MI355X only (got a non-GPU tensor); there is no CPU fallback")
+        if self.bidirectional:
+            if lengths is not None:
+                lengths = lengths.to(device=input.device, dtype=torch.int32).contiguous()
+            out, hn, cn, _, _, _ = torch.ops.xcp.lstm_bidir(
+                input, self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0,
+                self.weight_ih_l0_reverse, self.weight_hh_l0_reverse, self.bias_ih_l0_reverse,
+                self.bias_hh_l0_reverse, *((h0, c0) if hx is not None else (None, None)), lengths,
+                int(self.xcp_kernel))
+            return out.to(input.dtype), (hn, cn)
         if hx is not None:
             if lengths is not None:
                 lengths = lengths.to(device=input.device, dtype=torch.int32).contiguous()
@@ -97,7 +117,8 @@ class LSTM(nn.LSTM):
         return lengths
 
     def _check_hx(self, hx, input):  # noqa: A002
-        """(h0, c0), each floating [1, B, H] on the input's device; refused in nn.LSTM's words where it has any"""
+        """(h0, c0), each floating [D, B, H] (D directions) on the input's device; refused in nn.LSTM's words
+        where it has any"""
         if not isinstance(hx, (tuple, list)) or len(hx) != 2 or not all(torch.is_tensor(t) for t in hx):
             raise ValueError("hx must be a tuple of two tensors (h_0, c_0)")
         B, H = input.shape[0], self.hidden_size
@@ -105,8 +126,9 @@ class LSTM(nn.LSTM):
             if t.dim() != 3:
                 raise RuntimeError("For batched 3-D input, hx and cx should also be 3-D but got "
                                    f"({hx[0].dim()}-D, {hx[1].dim()}-D) tensors")
-            if tuple(t.shape) != (1, B, H):
-                raise RuntimeError(f"Expected hidden[{i}] size {(1, B, H)}, got {list(t.shape)}")
+            D = 2 if self.bidirectional else 1
+            if tuple(t.shape) != (D, B, H):
+                raise RuntimeError(f"Expected hidden[{i}] size {(D, B, H)}, got {list(t.shape)}")
             if not t.is_floating_point():
                 raise ValueError(f"hx[{i}] must be a floating-point tensor, got {t.dtype}")
             if t.device != input.device:

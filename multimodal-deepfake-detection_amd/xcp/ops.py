@@ -706,3 +706,55 @@ def lstm_bwd(dout, dhn, dcn, whh, cst, gates, dgates, B, T, H, kernel=0, lens=No
         _lib.call("xcp_lstm_bwd_varlen", *ptrs, _p(lens), B, T, H, kernel, stream())
 
 
+# Both directions of time (nn.LSTM(I, H, 1, batch_first=True, bidirectional=True)).  dirs: 1 = the forward
+# direction, 2 = the reverse one, 3 = both; D = 1, 1, 2 slots on the leading axis of every stacked tensor
+# (whh [D, 4H, H], bih / bhh [D, 4H], xproj / gates / dgates [D, B*T, 4H], hprev / cst [D, B, T, H], h0 / c0 /
+# hn / cn / dhn / dcn / dh0 / dc0 [D, B, H]); out / dout are [B, T, D*H].  Never the persistent kernels.
+def _dir_slots(dirs):
+    if dirs not in (1, 2, 3):
+        raise ValueError(f"dirs must be 1 (forward), 2 (reverse) or 3 (both), got {dirs}")
+    return 2 if dirs == 3 else 1
+
+
+def _check_dir_state(t, name, ref, D, B, H):
+    if (t.dtype != torch.float32 or t.device != ref.device or tuple(t.shape) != (D, B, H) or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous fp32 [{D}, {B}, {H}] tensor on {ref.device}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+
+
+def lstm_dir_needs_whhT(B, H, kernel=0):
+    return _lib.call("xcp_lstm_dir_needs_whhT", B, H, kernel) != 0
+
+
+def lstm_fwd_dir(xproj, whh, whhT, bih, bhh, out, hprev, cst, gates, hn, cn, B, T, H, dirs, kernel=0, lens=None,
+                 h0=None, c0=None):
+    D = _dir_slots(dirs)
+    if (h0 is None) != (c0 is None):
+        raise ValueError("h0 and c0 are given together")
+    if tuple(out.shape) != (B, T, D * H) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous [{B}, {T}, {D * H}] tensor, got {tuple(out.shape)}")
+    for t, name in ((h0, "h0"), (c0, "c0"), (hn, "hn"), (cn, "cn")):
+        if t is not None:
+            _check_dir_state(t, name, out, D, B, H)
+    if lens is not None:
+        _check_lens(lens, out, B)
+    _lib.call("xcp_lstm_fwd_dir", *(_p(t) for t in (xproj, whh, whhT, bih, bhh, h0, c0, out, hprev, cst, gates, hn, cn,
+                                                    lens)), B, T, H, kernel, dirs, stream())
+
+
+def lstm_bwd_dir(dout, dhn, dcn, whh, cst, gates, dgates, B, T, H, dirs, kernel=0, lens=None, c0=None, dh0=None,
+                 dc0=None):
+    D = _dir_slots(dirs)
+    if dout is not None and (tuple(dout.shape) != (B, T, D * H) or not dout.is_contiguous()):
+        raise ValueError(f"dout must be a contiguous [{B}, {T}, {D * H}] tensor, got {tuple(dout.shape)}")
+    for t, name in ((dhn, "dhn"), (dcn, "dcn"), (c0, "c0"), (dh0, "dh0"), (dc0, "dc0")):
+        if t is not None:
+            _check_dir_state(t, name, dgates, D, B, H)
+    if lens is not None:
+        _check_lens(lens, dgates, B)
+    # per-step kernels: per direction a cell-gradient carry [B][H] and W_hh^T [H][4H]
+    work = torch.empty(D * (B * H + 4 * H * H), device=whh.device, dtype=torch.float32)
+    _lib.call("xcp_lstm_bwd_dir", *(_p(t) for t in (dout, dhn, dcn, whh, c0, cst, gates, dgates, dh0, dc0, work, lens)),
+              B, T, H, kernel, dirs, stream())
+
+

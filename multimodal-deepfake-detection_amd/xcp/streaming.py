@@ -23,6 +23,9 @@ def score_in_chunks(model, clips, seq_lengths=None, chunk=16):
     backbone still runs over padded frames, as ``extract_features`` always does."""
     if clips.dim() != 5:
         raise ValueError("score_in_chunks: clips must be [B, T, 3, H, W]")
+    if getattr(model.lstm, "bidirectional", False):
+        raise ValueError("score_in_chunks: a bidirectional model cannot be scored in chunks (its reverse direction "
+                         "needs the clip's future frames); score the whole clip with model(features, seq_lengths)")
     chunk = int(chunk)
     if chunk < 1:
         raise ValueError("score_in_chunks: chunk must be at least 1 frame")

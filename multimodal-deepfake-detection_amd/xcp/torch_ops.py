@@ -660,8 +660,142 @@ def _lstm_state_bwd(ctx, dout, dhn, dcn, *_):
 lstm_state.register_autograd(_lstm_state_bwd, setup_context=_lstm_state_setup)
 
 
+# xcp::lstm_bidir / xcp::lstm_bidir_backward: both directions of time.  Everything per direction is stacked on a
+# leading axis of 2 (forward, reverse) and the two recurrences share their launches (lstm.hip, "Directions").
+_LstmBidirGrads = Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]
+
+
+@torch.library.custom_op("xcp::lstm_bidir", mutates_args=(), device_types="cuda")
+def lstm_bidir(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor, w_ih_r: Tensor, w_hh_r: Tensor,
+               b_ih_r: Tensor, b_hh_r: Tensor, h0: Optional[Tensor], c0: Optional[Tensor], lengths: Optional[Tensor],
+               kernel: int) -> _LstmOut:
+    """``nn.LSTM(I, H, 1, batch_first=True, bidirectional=True)`` forward, optionally from a state h0 / c0
+    [2, B, H] (given together) and with per-clip lengths (int32 [B] on x's device: the semantics of
+    pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length=T)).  The reverse direction reads each
+    clip backwards from its own last frame.  One fp32 GEMM per direction projects the input; the two recurrences
+    run in the same launches and write out [B, T, 2H] in place.  Returns (out, h_n [2, B, H], c_n [2, B, H]) and
+    the saved state (hprev, cst [2, B, T, H], activated gates [2, B*T, 4H])."""
+    with ops.device_guard(x):
+        ops.check_gpu(x, w_ih)
+        if (h0 is None) != (c0 is None):
+            raise ValueError("h0 and c0 are given together")
+        B, T, I = x.shape
+        H = w_hh.shape[1]
+        f = dict(device=x.device, dtype=torch.float32)
+        xf = x.detach().float().contiguous()
+        xproj = torch.empty(2, B * T, 4 * H, **f)
+        for d, w in enumerate((w_ih, w_ih_r)):
+            ops.gemm_nt(xf, w.detach().float().contiguous(), xproj[d], B * T, 4 * H, I)
+        stack = lambda a, b: torch.stack((a.detach().float(), b.detach().float())).contiguous()   # noqa: E731
+        whh = stack(w_hh, w_hh_r)
+        whhT = None
+        if ops.lstm_dir_needs_whhT(B, H, kernel):
+            whhT = torch.empty(2, H, 4 * H, **f)
+            for d in range(2):
+                ops.permute3(whh[d], whhT[d], 4 * H, H, 1, (1, 0, 2))
+        if h0 is not None:
+            h0, c0 = h0.detach().float().contiguous(), c0.detach().float().contiguous()
+        out = torch.empty(B, T, 2 * H, **f)
+        hprev, cst = torch.empty(2, B, T, H, **f), torch.empty(2, B, T, H, **f)
+        gates = torch.empty(2, B * T, 4 * H, **f)
+        hn, cn = torch.empty(2, B, H, **f), torch.empty(2, B, H, **f)
+        ops.lstm_fwd_dir(xproj, whh, whhT, stack(b_ih, b_ih_r), stack(b_hh, b_hh_r), out, hprev, cst, gates, hn, cn,
+                         B, T, H, 3, kernel, lengths, h0, c0)
+        return out, hn, cn, hprev, cst, gates
+
+
+@lstm_bidir.register_fake
+def _(x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, h0, c0, lengths, kernel):
+    B, T, _ = x.shape
+    H = w_hh.shape[1]
+    f = dict(device=x.device, dtype=torch.float32)
+    return (torch.empty(B, T, 2 * H, **f), torch.empty(2, B, H, **f), torch.empty(2, B, H, **f),
+            torch.empty(2, B, T, H, **f), torch.empty(2, B, T, H, **f), torch.empty(2, B * T, 4 * H, **f))
+
+
+@torch.library.custom_op("xcp::lstm_bidir_backward", mutates_args=(), device_types="cuda")
+def lstm_bidir_backward(dout: Optional[Tensor], dhn: Optional[Tensor], dcn: Optional[Tensor], x: Tensor, w_ih: Tensor,
+                        w_hh: Tensor, w_ih_r: Tensor, w_hh_r: Tensor, c0: Optional[Tensor], hprev: Tensor, cst: Tensor,
+                        gates: Tensor, lengths: Optional[Tensor], kernel: int, need_dx: bool, need_dh0: bool,
+                        need_dc0: bool) -> _LstmBidirGrads:
+    """(dx, dw_ih, dw_hh, db, dw_ih_r, dw_hh_r, db_r, dh0, dc0); dx is the sum of the two directions' input
+    gradients ([B, T, I], or empty when not wanted), dh0 / dc0 are [2, B, H], or empty when not wanted."""
+    with ops.device_guard(x):
+        B, T, I = x.shape
+        H = w_hh.shape[1]
+        M = B * T
+        f = dict(device=x.device, dtype=torch.float32)
+        xf = x.detach().float().contiguous()
+        f32 = lambda t: None if t is None else t.detach().float().contiguous()   # noqa: E731
+        dgates = torch.empty(2, M, 4 * H, **f)
+        state = lambda want: torch.empty((2, B, H) if want else 0, **f)   # noqa: E731
+        dh0, dc0 = state(need_dh0), state(need_dc0)
+        whh = torch.stack((w_hh.detach().float(), w_hh_r.detach().float())).contiguous()
+        ops.lstm_bwd_dir(f32(dout), f32(dhn), f32(dcn), whh, cst, gates, dgates, B, T, H, 3, kernel, lengths,
+                         c0=f32(c0), dh0=dh0 if need_dh0 else None, dc0=dc0 if need_dc0 else None)
+        grads = []
+        dx = torch.empty(B, T, I, **f) if need_dx else torch.empty(0, **f)
+        for d, w in enumerate((w_ih, w_ih_r)):
+            dw_ih = torch.empty(4 * H, I, **f)
+            ops.weight_grad(dgates[d], xf, M, 4 * H, I, dw_ih)
+            dw_hh = torch.empty(4 * H, H, **f)
+            ops.weight_grad(dgates[d], hprev[d], M, 4 * H, H, dw_hh)
+            db = torch.empty(4 * H, **f)
+            ops.reduce_slabs(dgates[d], M, 4 * H, db)
+            grads += [dw_ih, dw_hh, db]
+            if need_dx:   # no accumulating NT GEMM here: the reverse direction's share is added
+                wT = torch.empty(I * 4 * H, **f)
+                ops.permute3(w.detach().float().contiguous(), wT, 4 * H, I, 1, (1, 0, 2))
+                part = dx if d == 0 else torch.empty(B, T, I, **f)
+                ops.gemm_nt(dgates[d], wT, part, M, I, 4 * H)
+                if d == 1:
+                    dx.add_(part)
+        return (dx, *grads, dh0, dc0)
+
+
+@lstm_bidir_backward.register_fake
+def _(dout, dhn, dcn, x, w_ih, w_hh, w_ih_r, w_hh_r, c0, hprev, cst, gates, lengths, kernel, need_dx, need_dh0,
+      need_dc0):
+    B, T, I = x.shape
+    H = w_hh.shape[1]
+    f = dict(device=x.device, dtype=torch.float32)
+    state = lambda want: torch.empty((2, B, H) if want else 0, **f)   # noqa: E731
+    per = lambda: (torch.empty(4 * H, I, **f), torch.empty(4 * H, H, **f), torch.empty(4 * H, **f))   # noqa: E731
+    return (torch.empty(B, T, I, **f) if need_dx else torch.empty(0, **f), *per(), *per(), state(need_dh0),
+            state(need_dc0))
+
+
+def _lstm_bidir_setup(ctx, inputs, output):
+    x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, h0, c0, lengths, kernel = inputs
+    out, hn, cn, hprev, cst, gates = output
+    ctx.has_state, ctx.has_lens = c0 is not None, lengths is not None
+    ctx.save_for_backward(x, w_ih, w_hh, w_ih_r, w_hh_r, hprev, cst, gates, *((c0,) if ctx.has_state else ()),
+                          *((lengths,) if ctx.has_lens else ()))
+    ctx.kernel = kernel
+    ctx.x_dtype = x.dtype
+    ctx.h_dtype, ctx.c_dtype = (h0.dtype, c0.dtype) if ctx.has_state else (None, None)
+    ctx.mark_non_differentiable(hprev, cst, gates)
+
+
+def _lstm_bidir_bwd(ctx, dout, dhn, dcn, *_):
+    x, w_ih, w_hh, w_ih_r, w_hh_r, hprev, cst, gates, *rest = ctx.saved_tensors
+    c0 = rest.pop(0) if ctx.has_state else None
+    lengths = rest.pop(0) if ctx.has_lens else None
+    need_dx = ctx.needs_input_grad[0]
+    need_dh0, need_dc0 = ctx.has_state and ctx.needs_input_grad[9], ctx.has_state and ctx.needs_input_grad[10]
+    dx, dw_ih, dw_hh, db, dw_ih_r, dw_hh_r, db_r, dh0, dc0 = torch.ops.xcp.lstm_bidir_backward(
+        dout, dhn, dcn, x, w_ih, w_hh, w_ih_r, w_hh_r, c0, hprev, cst, gates, lengths, ctx.kernel, need_dx, need_dh0,
+        need_dc0)
+    return (dx.to(ctx.x_dtype) if need_dx else None, dw_ih, dw_hh, db, db.clone(), dw_ih_r, dw_hh_r, db_r,
+            db_r.clone(), dh0.to(ctx.h_dtype) if need_dh0 else None, dc0.to(ctx.c_dtype) if need_dc0 else None, None,
+            None)
+
+
+lstm_bidir.register_autograd(_lstm_bidir_bwd, setup_context=_lstm_bidir_setup)
+
+
 OPS: List[str] = ["dwconv3x3", "dwconv3x3_backward", "pointwise", "pointwise_backward", "batch_norm",
                   "batch_norm_backward", "max_pool3x3s2", "max_pool3x3s2_backward", "stem_conv1", "stem_conv1_wgrad",
                   "stem_conv1_dgrad",
                   "stem_conv2", "stem_conv2_backward", "lstm", "lstm_backward", "lstm_varlen", "lstm_varlen_backward",
-                  "lstm_state", "lstm_state_backward"]
+                  "lstm_state", "lstm_state_backward", "lstm_bidir", "lstm_bidir_backward"]
