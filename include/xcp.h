@@ -270,6 +270,37 @@ int xcp_clip_augment(const unsigned char* in, const int* len, const int* tab, vo
  * weight formulas in fp32); MFCC frames [B*T*3][13][1] -> [B*T*3][64][64] */
 int xcp_resize_bilinear(const float* in, float* out, int NC, int IH, int IW, int OH, int OW, xcp_stream_t stream);
 
+/* ---- audio front end, waveform -> MFCC (wavfake_audio_dataset.py:43: librosa.feature.mfcc(y, sr=16000,
+ * n_mfcc=13, n_fft=400, hop_length=160), then a slice of frames) ----
+ * wav [B][Nmax] fp32 (wav_i16 0) or int16 (1: v / 32768.f), len [B] int32, tab [B][XCP_MFCC_COLS] int32 or
+ * null (0 shift, 1 f0, 2 gain as fp32 bits, 3 unused; null: 0, 0, 1.f), all device.  The tables are fp32
+ * INPUTS (xcp/audio.py MfccPlan builds them in fp64): win [n_fft] periodic Hann; tw [n_fft][2] (cos, sin)
+ * (2 pi j / n_fft); mel_fc [n_mels][2] int32 (first bin, count) and mel_w [n_mels][mel_pitch] the Slaney
+ * filterbank per filter; dct [n_mfcc][n_mels] orthonormal DCT-II rows.  n_fft even in [16, 1024], hop >= 1,
+ * n_mfcc <= n_mels <= 128, Nmax < 2^30; anything else returns XCP_EINVAL before any launch.
+ * Per clip: n = clamp(len, 0, Nmax) - shift usable samples y[i] = wav[shift + i] * gain; Fall = 1 + n / hop
+ * frames (0 for n <= 0), frame f = y[f hop - n_fft / 2 ... + n_fft), zeros outside [0, n);
+ * P_k = |sum_n y w (cos - i sin)|^2, k <= n_fft / 2, fp32, the direct n_fft-term sum;
+ * L_j = 10 log10f(max(sum_k M[j][k] P_k, amin)).
+ * xcp_mfcc_logmel writes L of every frame to ws [B][Fmax][n_mels], Fmax = 1 + Nmax / hop, and one maximum
+ * per workgroup behind it (xcp_mfcc_ws_bytes sizes ws; -1: bad geometry or 2 GiB and more; a workgroup
+ * walks xcp_mfcc_run_frames(n_fft, hop) consecutive frames, 8 unless hop is large).
+ * xcp_mfcc_dct: L = max(L, Lmax - top_db) if use_floor, Lmax over all Fall frames of the clip;
+ * out [B][Tout][channels][n_mfcc] of dtype (bf16: nearest even), row t = dct L of frame f0 + t, written
+ * channels times; out_len[b] = min(Tout, max(0, Fall - f0)), rows t >= out_len[b] zero.  The kernels
+ * clamp shift to [0, Nmax] and f0 to >= 0 and load wav only inside [b][0 .. Nmax).  No float atomics, no
+ * host read, no allocation: the pair can be captured in a graph and replayed after wav, len and tab were
+ * rewritten in place. */
+#define XCP_MFCC_COLS 4
+int xcp_mfcc_run_frames(int n_fft, int hop);
+int xcp_mfcc_ws_bytes(int B, int Nmax, int n_fft, int hop, int n_mels);
+int xcp_mfcc_logmel(const void* wav, int wav_i16, const int* len, const int* tab, const float* win, const float* tw,
+                    const int* mel_fc, const float* mel_w, int mel_pitch, float* ws, int B, int Nmax, int n_fft, int hop,
+                    int n_mels, float amin, xcp_stream_t stream);
+int xcp_mfcc_dct(const float* ws, const int* len, const int* tab, const float* dct, void* out, int* out_len, int B, int Nmax,
+                 int n_fft, int hop, int n_mels, int n_mfcc, int Tout, int channels, int use_floor, float top_db, int dtype,
+                 xcp_stream_t stream);
+
 /* ---- training step (train_visual.py:575-577): clip_grad_norm_ + Adam (L2 weight decay) ----
  * tab: DEVICE [nchunks][6] int64 (param, grad, exp_avg, exp_avg_sq, first element, length <= 16384),
  * all fp32.  xcp_opt_sumsq: out[0] = min(1, max_norm / (||g|| + 1e-6)) (1 if max_norm <= 0),

@@ -14,6 +14,7 @@ Layout:
   attribution.py  input_gradient: d(score)/d(frames) of a clip model (saliency, FGSM / PGD)
   streaming.py    score_in_chunks: a long clip scored chunk by chunk with the LSTM state carried
   augment.py      ClipAugment / AugmentParams: per-clip crop, flip, colour, erase, frame sampling in one kernel
+  audio.py        MfccConfig / MfccPlan / WaveAugment / WaveFrontEnd: waveform -> MFCC input of XceptionLSTMA in two kernels
   heads.py      ArcFace head / CB-focal loss on HIP kernels; metrics.py: ROC / EER / pAUC
 
 Precision of the backbone (activations / GEMM operands; accumulation is fp32, master
@@ -63,6 +64,7 @@ def precision(dt):
 from .attribution import input_gradient  # noqa: E402,F401  (d(score)/d(frames) of a clip model)
 from .streaming import score_in_chunks  # noqa: E402,F401  (a long clip, chunk by chunk, LSTM state carried)
 from .augment import AugmentParams, ClipAugment, augment_reference  # noqa: E402,F401  (GPU clip augmentation)
+from .audio import MfccConfig, MfccPlan, WaveAugment, WaveFrontEnd, WaveParams, mfcc_reference  # noqa: E402,F401  (GPU MFCC front end)
 
 
 def library_path():

@@ -78,6 +78,10 @@ SIGNATURES = {
     "xcp_resize_bilinear": [P, P, I, I, I, I, I, P],
     "xcp_frames_prep": [P, P, P, I, I, I, I, I, I, I, I, P],
     "xcp_clip_augment": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
+    "xcp_mfcc_run_frames": [I, I],
+    "xcp_mfcc_ws_bytes": [I, I, I, I, I],
+    "xcp_mfcc_logmel": [P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, P],
+    "xcp_mfcc_dct": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, I, P],
     "xcp_opt_sumsq": [P, I, P, F, P, P],
     "xcp_opt_adam": [P, I, P, F, F, F, F, F, F, F, P],
     "xcp_opt_adam_dev": [P, I, P, F, D, D, F, F, P, P],
@@ -116,7 +120,7 @@ SIZE_QUERIES = {"xcp_permute3_blocks", "xcp_sep_fwd_parts", "xcp_gemm_tn_rows_pe
                 "xcp_colreduce_groups", "xcp_unit_bwd_rows_per_split",
                 "xcp_conv1_wgrad_parts", "xcp_conv1_wgrad_fused", "xcp_conv1_fwd_parts", "xcp_lstm_needs_whhT", "xcp_conv3x3_parts", "xcp_conv3x3_wgrad_parts",
                 "xcp_maxpool_bwd_bnred_parts", "xcp_lstm_sync_error", "xcp_lstm_varlen_needs_whhT",
-                "xcp_lstm_state_needs_whhT", "xcp_lstm_dir_needs_whhT"}
+                "xcp_lstm_state_needs_whhT", "xcp_lstm_dir_needs_whhT", "xcp_mfcc_run_frames", "xcp_mfcc_ws_bytes"}
 
 _lib = None
 

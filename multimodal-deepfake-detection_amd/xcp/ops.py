@@ -531,6 +531,68 @@ def clip_augment(frames, lengths, params, size, out_frames=None, dtype=torch.flo
     return (out.permute(0, 1, 4, 2, 3) if channels_last else out), out_len
 
 
+def mfcc(wav, lengths, plan, table=None, out_frames=None, channels=3, dtype=torch.float32):
+    """Padded PCM waveforms -> MFCC frames in two kernels (csrc/mfcc.hip; xcp.audio states the arithmetic
+    and restates it in fp64).  wav: fp32 or int16 [B, Nmax]; lengths: int32 [B]; plan: an
+    ``xcp.audio.MfccPlan``; table: an ``xcp.audio.WaveParams`` (validated here, then packed and copied to
+    the device), its packed device form ``table.to(device)``, int32 [B, 4], which the kernels clamp
+    instead, or None (no shift, f0 = 0, gain 1).  out_frames: Tout (default 1 + Nmax // hop, every frame
+    the batch can hold).  -> (mfcc [B, Tout, channels, n_mfcc], or [B, Tout, n_mfcc] for channels = 1, of
+    ``dtype``; out_len int32 [B]).  Stream-ordered, nothing read back: a call can be captured in a graph
+    and replayed after wav, lengths and the device table were rewritten in place."""
+    from . import torch_ops  # noqa: F401  (registers torch.ops.xcp.mfcc)
+    from .audio import WAVE_COLS, MfccPlan, WaveParams
+    if not isinstance(plan, MfccPlan):
+        raise ValueError("mfcc: plan is an xcp.audio.MfccPlan")
+    if not torch.is_tensor(wav) or wav.dim() != 2 or wav.dtype not in (torch.float32, torch.int16) or not wav.is_contiguous():
+        raise ValueError("mfcc: wav is a contiguous fp32 or int16 [B, Nmax] tensor")
+    B, Nmax = wav.shape
+    if B < 1 or Nmax < 1:
+        raise ValueError("mfcc: wav is empty")
+    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) \
+            or not lengths.is_contiguous() or lengths.device != wav.device:
+        raise ValueError("mfcc: lengths is a contiguous int32 [B] tensor on wav's device")
+    if dtype not in DT:
+        raise ValueError("mfcc: the output is fp32 or bf16")
+    cfg = plan.cfg
+    Tout = 1 + Nmax // cfg.hop if out_frames is None else int(out_frames)
+    channels = int(channels)
+    if Tout < 1 or channels < 1:
+        raise ValueError("mfcc: out_frames and channels must be positive")
+    if isinstance(table, WaveParams):
+        table.validate(B, Nmax)
+        table = table.to(wav.device)
+    if table is not None and (not torch.is_tensor(table) or table.dtype != torch.int32 or tuple(table.shape) != (B, WAVE_COLS)
+                              or not table.is_contiguous() or table.device != wav.device):
+        raise ValueError(f"mfcc: the device table is a contiguous int32 [B, {WAVE_COLS}] tensor on wav's device")
+    if not wav.is_meta:
+        check_gpu(wav)
+    d = plan.to(wav.device)
+    out, out_len = torch.ops.xcp.mfcc(wav, lengths, table, d.win, d.tw, d.mel_fc, d.mel_w, d.dct, cfg.hop, Tout, channels,
+                                      dtype == torch.bfloat16, cfg.top_db is not None,
+                                      0.0 if cfg.top_db is None else cfg.top_db, cfg.amin)
+    return (out.view(B, Tout, cfg.n_mfcc) if channels == 1 else out), out_len
+
+
+def mfcc_launch(wav, lengths, table, win, tw, mel_fc, mel_w, dct, hop, Tout, channels, dtype, use_floor, top_db, amin):
+    """The two launches of ``mfcc`` on device tensors (the body of torch.ops.xcp.mfcc)."""
+    check_gpu(wav, lengths, table, win, tw, mel_fc, mel_w, dct)
+    B, Nmax = wav.shape
+    n_fft, (n_mels, pitch), n_mfcc = win.numel(), mel_w.shape, dct.shape[0]
+    nbytes = _lib.call("xcp_mfcc_ws_bytes", B, Nmax, n_fft, hop, n_mels)
+    if nbytes < 0:
+        raise ValueError(f"mfcc: unsupported geometry (B {B}, Nmax {Nmax}, n_fft {n_fft}, hop {hop}, n_mels {n_mels}) "
+                         "or a workspace of 2 GiB and more")
+    ws = torch.empty(nbytes // 4, device=wav.device, dtype=torch.float32)
+    out = torch.empty((B, Tout, channels, n_mfcc), device=wav.device, dtype=dtype)
+    out_len = torch.empty(B, device=wav.device, dtype=torch.int32)
+    _lib.call("xcp_mfcc_logmel", _p(wav), 1 if wav.dtype == torch.int16 else 0, _p(lengths), _p(table), _p(win), _p(tw),
+              _p(mel_fc), _p(mel_w), pitch, _p(ws), B, Nmax, n_fft, hop, n_mels, amin, stream())
+    _lib.call("xcp_mfcc_dct", _p(ws), _p(lengths), _p(table), _p(dct), _p(out), _p(out_len), B, Nmax, n_fft, hop, n_mels,
+              n_mfcc, Tout, channels, 1 if use_floor else 0, top_db, DT[dtype], stream())
+    return out, out_len
+
+
 def resize_bilinear(x, size):
     """F.interpolate(x, size, mode="bilinear", align_corners=False) for fp32 NCHW x on the GPU
     (the XceptionLSTMA front end, XceptionLSTMA.py:46)."""

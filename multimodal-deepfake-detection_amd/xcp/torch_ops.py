@@ -794,8 +794,28 @@ def _lstm_bidir_bwd(ctx, dout, dhn, dcn, *_):
 lstm_bidir.register_autograd(_lstm_bidir_bwd, setup_context=_lstm_bidir_setup)
 
 
+# ------------------------------------------------------------------ MFCC front end (xcp.audio, csrc/mfcc.hip)
+@torch.library.custom_op("xcp::mfcc", mutates_args=(), device_types="cuda")
+def mfcc(wav: Tensor, lengths: Tensor, table: Optional[Tensor], win: Tensor, tw: Tensor, mel_fc: Tensor, mel_w: Tensor,
+         dct: Tensor, hop: int, out_frames: int, channels: int, bf16_out: bool, use_floor: bool, top_db: float,
+         amin: float) -> Tuple[Tensor, Tensor]:
+    """wavfake_audio_dataset.py:43 (librosa.feature.mfcc + the frame slice) on padded waveforms; ``ops.mfcc``
+    validates and is the way in."""
+    with ops.device_guard(wav):
+        return ops.mfcc_launch(wav, lengths, table, win, tw, mel_fc, mel_w, dct, hop, out_frames, channels,
+                               torch.bfloat16 if bf16_out else torch.float32, use_floor, top_db, amin)
+
+
+@mfcc.register_fake
+def _(wav, lengths, table, win, tw, mel_fc, mel_w, dct, hop, out_frames, channels, bf16_out, use_floor, top_db, amin):
+    B = wav.shape[0]
+    return (torch.empty((B, out_frames, channels, dct.shape[0]), device=wav.device,
+                        dtype=torch.bfloat16 if bf16_out else torch.float32),
+            torch.empty((B,), device=wav.device, dtype=torch.int32))
+
+
 OPS: List[str] = ["dwconv3x3", "dwconv3x3_backward", "pointwise", "pointwise_backward", "batch_norm",
                   "batch_norm_backward", "max_pool3x3s2", "max_pool3x3s2_backward", "stem_conv1", "stem_conv1_wgrad",
                   "stem_conv1_dgrad",
                   "stem_conv2", "stem_conv2_backward", "lstm", "lstm_backward", "lstm_varlen", "lstm_varlen_backward",
-                  "lstm_state", "lstm_state_backward", "lstm_bidir", "lstm_bidir_backward"]
+                  "lstm_state", "lstm_state_backward", "lstm_bidir", "lstm_bidir_backward", "mfcc"]
