@@ -270,6 +270,27 @@ int xcp_clip_augment(const unsigned char* in, const int* len, const int* tab, vo
  * weight formulas in fp32); MFCC frames [B*T*3][13][1] -> [B*T*3][64][64] */
 int xcp_resize_bilinear(const float* in, float* out, int NC, int IH, int IW, int OH, int OW, xcp_stream_t stream);
 
+/* ---- class-activation maps (xcp.attribution; no reference op: build-defined) ----
+ * A, G: NHWC [N][HW][CP] of dtype (bf16 / fp32), CP % 8 == 0 the channel pitch, channels c >= C ignored
+ * whatever they hold.  act(a) = max(fmaf(a, a_scale[c], a_shift[c]), 0) when a_scale / a_shift ([C] fp32,
+ * both or neither) are given, else a.  raw [N][HW] fp32:
+ *   mode 0 (gradcam):  raw[n][p] = sum_c w[n][c] act(A[n][p][c]), w = alpha [N][C] fp32 if non-null, else
+ *                      w[n][c] = (sum_p G[n][p][c]) / HW formed by the kernel (G then required);
+ *   mode 1 (hirescam): raw[n][p] = sum_c G[n][p][c] act(A[n][p][c]); G required, alpha must be null.
+ * One workgroup per frame, each of A and G read once, fp32 accumulation, no atomics: two runs are
+ * bit-identical.  Any N, HW >= 1.  XCP_EINVAL: null A / raw, a size <= 0, C > CP, CP % 8, half a BN, the
+ * mode's operands as above.  XCP_EUNSUPPORTED: C > 2048 (the per-channel vectors' LDS), another dtype. */
+int xcp_cam(int dtype, int mode, const void* A, const float* a_scale, const float* a_shift, const void* G,
+            const float* alpha, float* raw, int N, int HW, int C, int CP, xcp_stream_t stream);
+/* no reference op: build-defined.  raw [B*T][h][w] fp32 -> out [B*T][OH][OW] fp32: r = max(raw, 0);
+ * normalize 1: r / max_p r at the low resolution (a frame without a positive value stays zero: no NaN);
+ * bilinear up-sampling, align_corners=False, xcp_resize_bilinear's arithmetic; every output of a normalized
+ * map lies in [0, 1].  len [B] int32 device or null: frames t >= len[b] are zero (no host read).
+ * h * w from 1 to 8192 and OW up to 2048 (the map and the output columns' indices and weights are staged in
+ * LDS; beyond: XCP_EUNSUPPORTED). */
+int xcp_cam_render(const float* raw, const int* len, float* out, int B, int T, int h, int w, int OH, int OW,
+                   int normalize, xcp_stream_t stream);
+
 /* ---- audio front end, waveform -> MFCC (wavfake_audio_dataset.py:43: librosa.feature.mfcc(y, sr=16000,
  * n_mfcc=13, n_fft=400, hop_length=160), then a slice of frames) ----
  * wav [B][Nmax] fp32 (wav_i16 0) or int16 (1: v / 32768.f), len [B] int32, tab [B][XCP_MFCC_COLS] int32 or

@@ -52,6 +52,12 @@ class XceptionLSTMA(nn.Module):
         frame_features = self.feature_extractor(frames)
         return frame_features.view(batch_size, time_steps, frame_features.shape[-1])
 
+    def input_frames(self, audio_batch):
+        """The backbone's input for ``audio_batch`` [B,T,3,n_mfcc]: fp32 [B*T,3,64,64], the images
+        ``extract_features`` feeds it (XceptionLSTMA.py:44-46).  ``xcp.grad_cam`` draws its maps over these."""
+        batch_size, time_steps, c, n_mfcc = audio_batch.shape
+        return ops.resize_bilinear(audio_batch.detach().reshape(batch_size * time_steps, c, n_mfcc, 1), (64, 64))
+
     def forward(self, features, seq_lengths=None):
         """``features`` [B,T,2048] -> clip probability [B,1].  With ``seq_lengths`` ([B], the loaders'
         per-clip frame counts of the zero-padded batch; train_visual.py:111) the head is fed the LSTM

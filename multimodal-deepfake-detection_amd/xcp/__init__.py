@@ -11,7 +11,8 @@ Layout:
   lstm.py       nn.LSTM drop-in on the fused LSTM kernels
   ddp.py        one-process-per-GPU data parallelism over RCCL
   optim.py      fused clip_grad_norm_ + Adam (a torch.optim.Optimizer)
-  attribution.py  input_gradient: d(score)/d(frames) of a clip model (saliency, FGSM / PGD)
+  attribution.py  input_gradient: d(score)/d(frames) of a clip model (saliency, FGSM / PGD); grad_cam /
+                  backbone_cam / frame_relevance: class-activation maps of a backbone layer, per-frame relevance
   streaming.py    score_in_chunks: a long clip scored chunk by chunk with the LSTM state carried
   augment.py      ClipAugment / AugmentParams: per-clip crop, flip, colour, erase, frame sampling in one kernel
   audio.py        MfccConfig / MfccPlan / WaveAugment / WaveFrontEnd: waveform -> MFCC input of XceptionLSTMA in two kernels
@@ -62,6 +63,7 @@ def precision(dt):
 
 
 from .attribution import input_gradient  # noqa: E402,F401  (d(score)/d(frames) of a clip model)
+from .attribution import backbone_cam, frame_relevance, grad_cam  # noqa: E402,F401  (class-activation maps)
 from .streaming import score_in_chunks  # noqa: E402,F401  (a long clip, chunk by chunk, LSTM state carried)
 from .augment import AugmentParams, ClipAugment, augment_reference  # noqa: E402,F401  (GPU clip augmentation)
 from .audio import MfccConfig, MfccPlan, WaveAugment, WaveFrontEnd, WaveParams, mfcc_reference  # noqa: E402,F401  (GPU MFCC front end)

@@ -76,6 +76,8 @@ SIGNATURES = {
     "xcp_permute3_batch": [P, I, I, P],
     "xcp_frames_u8_to_f32": [P, P, P, I, I, I, I, P],
     "xcp_resize_bilinear": [P, P, I, I, I, I, I, P],
+    "xcp_cam": [I, I, P, P, P, P, P, P, I, I, I, I, P],
+    "xcp_cam_render": [P, P, P, I, I, I, I, I, I, I, P],
     "xcp_frames_prep": [P, P, P, I, I, I, I, I, I, I, I, P],
     "xcp_clip_augment": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "xcp_mfcc_run_frames": [I, I],

@@ -464,8 +464,29 @@ class XceptionEngine:
 
     # ------------------------------------------------------------ backward
     INPUT = "<frames>"   # key of the input gradient in backward's result
+    TAP = "<tap>"        # key of a block output's gradient in backward's result
+    TAPS = tuple(f"block{k}" for k in range(1, 13))   # the block outputs a backward can tap
+    LAYERS = ("exit",) + TAPS   # what tap_activation names
 
-    def backward(self, S, dfeat, out=None, notify=None, need=None, input_grad=False):
+    def tap_activation(self, S, layer):
+        """The tensor ``layer`` names in the saved state of a forward(..., for_backward=True), for the
+        class-activation maps (xcp.attribution): (A, scale, shift, N, h, w, C, CP), A NHWC in the engine's
+        dtype at channel pitch CP.  "blockK": that Block's output (x + skip, before the next block's ReLU),
+        scale = shift = None.  "exit": conv4's raw output with BN4's scale / shift -- relu(bn4(conv4)), the
+        map the global average pool reads, exists only on load (avgpool_fwd)."""
+        if layer == "exit":
+            e4 = S["exit"][-1]
+            return e4["y"], e4["st"].scale, e4["st"].shift, S["N"], S["xH"], S["xW"], 2048, pc(2048)
+        if layer not in self.TAPS:
+            raise ValueError(f"xcp engine: unknown layer {layer!r}; one of {', '.join(self.LAYERS)}")
+        k = int(layer[5:])
+        C = self.blocks[k - 1].cout
+        if k == 12:
+            return S["x12"], None, None, S["N"], S["xH"], S["xW"], C, pc(C)
+        bs = S["blocks"][k]   # block k + 1, whose input is block k's output
+        return bs["x_in"], None, None, S["N"], bs["H"], bs["W"], C, pc(C)
+
+    def backward(self, S, dfeat, out=None, notify=None, need=None, input_grad=False, tap=None):
         """dfeat [N,2048] fp32 -> backbone parameter gradients, after a forward in either mode (train=False:
         the BatchNorms ran on their running statistics, which are constants of the step -- XCP_FIN_FROZEN).
 
@@ -475,11 +496,16 @@ class XceptionEngine:
         that produce the gradients of ``names`` are enqueued (side_stream: the stream the
         weight gradients run on, or None).  need (a set of parameter names; None: all): the others'
         stand-alone weight-gradient launches and slab reductions are skipped.  input_grad: also the
-        gradient w.r.t. the frames, fp32 [N,3,IH,IW], under the key ``XceptionEngine.INPUT``."""
+        gradient w.r.t. the frames, fp32 [N,3,IH,IW], under the key ``XceptionEngine.INPUT``.  tap
+        ("block1" .. "block12"): also the gradient w.r.t. that Block's output under the key
+        ``XceptionEngine.TAP``, in the engine's dtype, NHWC at the channel pitch (tap_activation's layout);
+        with an empty ``need`` and no input_grad the backward ends once the tap is produced."""
+        if tap is not None and tap not in self.TAPS:
+            raise ValueError(f"xcp engine: unknown tap {tap!r}; one of {', '.join(self.TAPS)}")
         with ops.device_guard(dfeat):
-            return self._backward(S, dfeat, out, notify, need, input_grad)
+            return self._backward(S, dfeat, out, notify, need, input_grad, tap)
 
-    def _backward(self, S, dfeat, out, notify, need=None, input_grad=False):
+    def _backward(self, S, dfeat, out, notify, need=None, input_grad=False, tap=None):
         pk = self.pack_bwd()
         m = self.model
         N = S["N"]
@@ -612,6 +638,22 @@ class XceptionEngine:
         dZ3, p3 = unit_bwd(u4, e4, dZ4, H, W, prev_st=e3["st"])
         dX, _ = unit_bwd(u3, e3, dZ3, H, W, part=p3)
         done()
+        # a tapped block output's gradient is the dX entering that block's backward; nothing else is wanted:
+        # the backward ends there (the side stream joined, the kept tensors released, as at the full end)
+        tap_k = int(tap[5:]) if tap is not None else -1
+        tap_only = tap is not None and need is not None and not need and not input_grad
+
+        def tapped():
+            grads[self.TAP] = dX
+            if tap_only:
+                if side is not None:
+                    main.wait_stream(side)
+                keep.clear()
+                done()
+            return tap_only
+
+        if tap_k == len(self.blocks) and tapped():
+            return grads
         # ---- blocks, last to first
         pre_part = part_in = None
         for k in range(len(self.blocks) - 1, -1, -1):
@@ -619,6 +661,8 @@ class XceptionEngine:
             dX, pre_part, part_in = self._block_bwd(self.blocks[k], S["blocks"][k], dX, N, pk, bn_bwd, unit_bwd,
                                                     wgrad, part_in, prev)
             done()
+            if k == tap_k and tapped():
+                return grads
         # ---- stem
         OH1, OW1, OH2, OW2 = S["OH1"], S["OW1"], S["OH2"], S["OW2"]
         rows1, rows2 = N * OH1 * OW1, N * OH2 * OW2

@@ -607,6 +607,49 @@ def resize_bilinear(x, size):
     return out
 
 
+CAM_GRADCAM, CAM_HIRESCAM = 0, 1
+CAM_MODES = {"gradcam": CAM_GRADCAM, "hirescam": CAM_HIRESCAM}
+
+
+def cam(A, N, HW, C, CP, G=None, alpha=None, a_scale=None, a_shift=None, mode=CAM_GRADCAM):
+    """Raw class-activation maps [N, HW] fp32 of an NHWC activation A [N, HW, CP] (bf16 or fp32; channels
+    c >= C ignored) and its gradient G (csrc/cam.hip): gradcam sums alpha[n, c] * A over c, alpha [N, C] fp32
+    given or the spatial mean of G; hirescam sums G * A.  a_scale / a_shift: A is a raw pointwise output,
+    relu(A * scale + shift) is formed on load."""
+    check_gpu(A, G, alpha, a_scale, a_shift)
+    if A.dtype not in DT or (G is not None and G.dtype != A.dtype):
+        raise ValueError("cam: A and G must both be bf16 or both fp32")
+    if A.numel() != N * HW * CP or (G is not None and G.numel() != N * HW * CP):
+        raise ValueError("cam: A and G must hold N * HW * CP elements")
+    if not A.is_contiguous() or (G is not None and not G.is_contiguous()):
+        raise ValueError("cam: A and G must be contiguous (NHWC at the channel pitch)")
+    for t, n, name in ((alpha, N * C, "alpha [N, C]"), (a_scale, C, "a_scale [C]"), (a_shift, C, "a_shift [C]")):
+        if t is not None and (t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous()):
+            raise ValueError(f"cam: {name} must be contiguous fp32")
+    raw = torch.empty((N, HW), device=A.device, dtype=torch.float32)
+    with _timed("cam", {"N": N, "HW": HW, "C": C, "mode": mode}):
+        _lib.call("xcp_cam", DT[A.dtype], mode, _p(A), _p(a_scale), _p(a_shift), _p(G), _p(alpha), _p(raw), N, HW, C, CP,
+                  stream())
+    return raw
+
+
+def cam_render(raw, size, lengths=None, normalize=True):
+    """raw [B, T, h, w] fp32 -> [B, T, OH, OW] fp32: relu, (normalize) / the frame's maximum, bilinear
+    up-sampling (align_corners=False); frames t >= lengths[b] (device int32 [B]) are zero."""
+    check_gpu(raw, lengths)
+    if raw.dtype != torch.float32 or raw.dim() != 4:
+        raise ValueError("cam_render: expects fp32 [B, T, h, w]")
+    B, T, h, w = raw.shape
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous()):
+        raise ValueError("cam_render: lengths must be a contiguous int32 [B]")
+    raw = raw.contiguous()
+    OH, OW = size
+    out = torch.empty((B, T, OH, OW), device=raw.device, dtype=torch.float32)
+    with _timed("cam_render", {"B": B, "T": T, "h": h, "w": w, "OH": OH, "OW": OW}):
+        _lib.call("xcp_cam_render", _p(raw), _p(lengths), _p(out), B, T, h, w, OH, OW, 1 if normalize else 0, stream())
+    return out
+
+
 def conv3x3_parts(mode, N, IH, IW):
     return _lib.call("xcp_conv3x3_parts", mode, N, IH, IW)
 

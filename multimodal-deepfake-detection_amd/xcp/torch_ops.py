@@ -814,8 +814,38 @@ def _(wav, lengths, table, win, tw, mel_fc, mel_w, dct, hop, out_frames, channel
             torch.empty((B,), device=wav.device, dtype=torch.int32))
 
 
+# ------------------------------------------------------------------ class-activation maps (xcp.attribution, csrc/cam.hip)
+@torch.library.custom_op("xcp::cam", mutates_args=(), device_types="cuda")
+def cam(A: Tensor, G: Optional[Tensor], alpha: Optional[Tensor], a_scale: Optional[Tensor], a_shift: Optional[Tensor],
+        C: int, mode: int) -> Tensor:
+    """Raw Grad-CAM (mode 0) / HiResCAM (mode 1) maps [N, HW] fp32 of an NHWC activation A [N, HW, CP] and its
+    gradient G; no reference op, no autograd: a map is a result, not a differentiable node."""
+    with ops.device_guard(A):
+        N, HW, CP = A.shape
+        return ops.cam(A, N, HW, C, CP, G=G, alpha=alpha, a_scale=a_scale, a_shift=a_shift, mode=mode)
+
+
+@cam.register_fake
+def _(A, G, alpha, a_scale, a_shift, C, mode):
+    return torch.empty((A.shape[0], A.shape[1]), device=A.device, dtype=torch.float32)
+
+
+@torch.library.custom_op("xcp::cam_render", mutates_args=(), device_types="cuda")
+def cam_render(raw: Tensor, lengths: Optional[Tensor], OH: int, OW: int, normalize: bool) -> Tensor:
+    """raw [B, T, h, w] -> heat maps [B, T, OH, OW] fp32 (relu, per-frame maximum, bilinear up-sampling, length
+    mask); no autograd."""
+    with ops.device_guard(raw):
+        return ops.cam_render(raw, (OH, OW), lengths, normalize)
+
+
+@cam_render.register_fake
+def _(raw, lengths, OH, OW, normalize):
+    return torch.empty((raw.shape[0], raw.shape[1], OH, OW), device=raw.device, dtype=torch.float32)
+
+
 OPS: List[str] = ["dwconv3x3", "dwconv3x3_backward", "pointwise", "pointwise_backward", "batch_norm",
                   "batch_norm_backward", "max_pool3x3s2", "max_pool3x3s2_backward", "stem_conv1", "stem_conv1_wgrad",
                   "stem_conv1_dgrad",
                   "stem_conv2", "stem_conv2_backward", "lstm", "lstm_backward", "lstm_varlen", "lstm_varlen_backward",
-                  "lstm_state", "lstm_state_backward", "lstm_bidir", "lstm_bidir_backward", "mfcc"]
+                  "lstm_state", "lstm_state_backward", "lstm_bidir", "lstm_bidir_backward", "mfcc", "cam",
+                  "cam_render"]
