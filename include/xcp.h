@@ -265,6 +265,21 @@ int xcp_frames_prep(const unsigned char* in, const int* len, void* out, int B, i
 int xcp_clip_augment(const unsigned char* in, const int* len, const int* tab, void* out, int* out_len, int B, int Tmax,
                      int Tout, int H, int W, int OH, int OW, int dtype, int nhwc, xcp_stream_t stream);
 
+/* ---- clip degradation: Gaussian blur, sensor noise, baseline 4:2:0 JPEG of the uint8 clip (no reference op:
+ * build-defined; xcp/degrade.py states the integer arithmetic, DESIGN.md section 4.6 the kernel) ----
+ * in, out [B][Tmax][H][W][3] uint8 (device; out must not alias in), len [B] int32, tab [B][XCP_DEG_COLS] int32
+ * (device), one row per clip, shared by its frames:
+ *   0 quality (0: no JPEG), 1 R (0: no blur), 2-9 w[0..7] (blur taps, 2048 per pass), 10 namp (0: no noise),
+ *   11 seed_lo, 12 seed_hi (Philox key), 13-15 unused.
+ * Per clip blur -> noise -> JPEG, each skipped when its parameter is 0; frames t >= clamp(len[b], 0, Tmax) are
+ * zero; real frames of a clip with all three 0 are copied.  Integer arithmetic throughout: byte for byte
+ * xcp.degrade.degrade_reference.  The kernel clamps quality to [0, 100], R to [0, 7], namp to [0, 1023]: no
+ * table reads or writes out of bounds.  Any H, W >= 1 with H * W * 3 < 2^31.  No host read, no allocation: a
+ * call can be captured in a graph and replayed after tab has been rewritten in place. */
+#define XCP_DEG_COLS 16
+int xcp_clip_degrade(const unsigned char* in, const int* len, const int* tab, unsigned char* out, int B, int Tmax,
+                     int H, int W, xcp_stream_t stream);
+
 /* ---- audio front end (XceptionLSTMA.py:44-46): F.interpolate(bilinear, align_corners=False) ----
  * out [NC][OH][OW] fp32 = bilinear resize of in [NC][IH][IW] fp32 (ATen's source-index and
  * weight formulas in fp32); MFCC frames [B*T*3][13][1] -> [B*T*3][64][64] */

@@ -105,10 +105,15 @@ class PinnedClipReader:
     ``xcp_clip_augment`` takes the place of ``xcp_frames_prep``: clips are
     ``[B, augment.frames or Tmax, 3, *augment.size]`` and the yielded lengths are the
     augmented clips' (frame sub-sampling shortens them).
+
+    ``degrade``: an ``xcp.degrade.ClipDegrade``.  The reader thread draws the batch's degradation
+    table the same way (``degrade_table``), and ``xcp_clip_degrade`` (blur, sensor noise, JPEG of
+    the uint8 clip on the device) runs ahead of ``xcp_clip_augment`` / ``xcp_frames_prep``, which
+    see a uint8 clip of the same shape.  ``None`` leaves every path as it is without it.
     """
 
     def __init__(self, folder_path, batch_size, device, size=None, dtype=torch.float32, channels_last=False,
-                 shuffle=False, seed=0, drop_last=False, augment=None):
+                 shuffle=False, seed=0, drop_last=False, augment=None, degrade=None):
         self.files = FaceDataset(folder_path).npy_files
         self.batch_size = batch_size
         self.device = torch.device(device)
@@ -116,6 +121,7 @@ class PinnedClipReader:
         self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
         self.epoch = 0
         self.augment = augment
+        self.degrade = degrade
         if augment is not None and size is not None and tuple(size) != tuple(augment.size):
             raise ValueError(f"size {tuple(size)} contradicts augment.size {tuple(augment.size)}")
 
@@ -124,6 +130,12 @@ class PinnedClipReader:
         index) and the batch's clip lengths and frame size only."""
         rng = np.random.default_rng([self.seed, epoch, index])
         return self.augment.sample(lengths.tolist(), H, W, rng)
+
+    def degrade_table(self, epoch, index, B):
+        """The DegradeParams of batch ``index`` of epoch ``epoch``: a function of (seed, epoch, index)
+        and the batch's clip count only (a stream of its own, apart from ``augment_table``'s)."""
+        rng = np.random.default_rng([self.seed, epoch, index, 1])
+        return self.degrade.sample(B, rng)
 
     def __len__(self):
         n = len(self.files)
@@ -169,7 +181,7 @@ class PinnedClipReader:
         import threading
         from xcp import ops
         batches = self.batches()
-        epoch, aug = self.epoch, self.augment
+        epoch, aug, deg = self.epoch, self.augment, self.degrade
         self.epoch += 1
         copy_stream = torch.cuda.Stream(self.device)
         bufs = [None, None]
@@ -177,6 +189,10 @@ class PinnedClipReader:
         if aug is not None:
             from xcp.augment import AUG_COLS
             tabs = [torch.empty((self.batch_size, AUG_COLS), dtype=torch.int32, pin_memory=True) for _ in range(2)]
+        dtabs = [None, None]                             # pinned int32 [batch_size, 16] degradation tables
+        if deg is not None:
+            from xcp.degrade import DEG_COLS
+            dtabs = [torch.empty((self.batch_size, DEG_COLS), dtype=torch.int32, pin_memory=True) for _ in range(2)]
         free = [threading.Event(), threading.Event()]   # host buffer may be refilled
         for e in free:
             e.set()
@@ -199,7 +215,10 @@ class PinnedClipReader:
                     if aug is not None:
                         table = self.augment_table(epoch, i, lengths, frames.shape[2], frames.shape[3]).pack(
                             tabs[slot][:len(paths)])
-                    q.put((slot, frames, labels, lengths, table))
+                    dtable = None
+                    if deg is not None:
+                        dtable = self.degrade_table(epoch, i, len(paths)).pack(dtabs[slot][:len(paths)])
+                    q.put((slot, frames, labels, lengths, table, dtable))
                 q.put(None)
             except BaseException as exc:   # surfaced on the consumer side
                 q.put(exc)
@@ -213,12 +232,13 @@ class PinnedClipReader:
                     break
                 if isinstance(item, BaseException):
                     raise item
-                slot, frames, labels, lengths, table = item
+                slot, frames, labels, lengths, table, dtable = item
                 with torch.cuda.stream(copy_stream):
                     f = frames.to(self.device, non_blocking=True)
                     ln = lengths.to(self.device, non_blocking=True)
                     lab = labels.to(self.device, non_blocking=True)
                     tab = None if table is None else table.to(self.device, non_blocking=True)
+                    dtab = None if dtable is None else dtable.to(self.device, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(copy_stream)
                 copied[slot] = ev
@@ -227,6 +247,9 @@ class PinnedClipReader:
                 cur.wait_event(ev)
                 for t in (f, ln, lab):
                     t.record_stream(cur)
+                if dtab is not None:
+                    dtab.record_stream(cur)
+                    f = ops.clip_degrade(f, ln, dtab)
                 if tab is None:
                     clips = ops.frames_prep(f, ln, self.size, self.dtype, self.channels_last)
                 else:

@@ -15,6 +15,7 @@ Layout:
                   backbone_cam / frame_relevance: class-activation maps of a backbone layer, per-frame relevance
   streaming.py    score_in_chunks: a long clip scored chunk by chunk with the LSTM state carried
   augment.py      ClipAugment / AugmentParams: per-clip crop, flip, colour, erase, frame sampling in one kernel
+  degrade.py      ClipDegrade / DegradeParams / robustness_sweep: blur, sensor noise and JPEG of the uint8 clip in one kernel
   audio.py        MfccConfig / MfccPlan / WaveAugment / WaveFrontEnd: waveform -> MFCC input of XceptionLSTMA in two kernels
   heads.py      ArcFace head / CB-focal loss on HIP kernels; metrics.py: ROC / EER / pAUC
 
@@ -66,6 +67,7 @@ from .attribution import input_gradient  # noqa: E402,F401  (d(score)/d(frames) 
 from .attribution import backbone_cam, frame_relevance, grad_cam  # noqa: E402,F401  (class-activation maps)
 from .streaming import score_in_chunks  # noqa: E402,F401  (a long clip, chunk by chunk, LSTM state carried)
 from .augment import AugmentParams, ClipAugment, augment_reference  # noqa: E402,F401  (GPU clip augmentation)
+from .degrade import ClipDegrade, DegradeParams, degrade_reference, robustness_sweep  # noqa: E402,F401  (GPU blur / noise / JPEG)
 from .audio import MfccConfig, MfccPlan, WaveAugment, WaveFrontEnd, WaveParams, mfcc_reference  # noqa: E402,F401  (GPU MFCC front end)
 
 

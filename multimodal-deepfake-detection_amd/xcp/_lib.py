@@ -80,6 +80,7 @@ SIGNATURES = {
     "xcp_cam_render": [P, P, P, I, I, I, I, I, I, I, P],
     "xcp_frames_prep": [P, P, P, I, I, I, I, I, I, I, I, P],
     "xcp_clip_augment": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
+    "xcp_clip_degrade": [P, P, P, P, I, I, I, I, P],
     "xcp_mfcc_run_frames": [I, I],
     "xcp_mfcc_ws_bytes": [I, I, I, I, I],
     "xcp_mfcc_logmel": [P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, P],

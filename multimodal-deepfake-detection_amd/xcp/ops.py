@@ -531,6 +531,44 @@ def clip_augment(frames, lengths, params, size, out_frames=None, dtype=torch.flo
     return (out.permute(0, 1, 4, 2, 3) if channels_last else out), out_len
 
 
+def clip_degrade(frames, lengths, params, out=None):
+    """uint8 [B, T, H, W, 3] frames (device) + int32 [B] lengths + a per-clip table -> the degraded uint8
+    clip of the same shape, one kernel: Gaussian blur, sensor noise, baseline 4:2:0 JPEG, per clip and in
+    that order, frames past a clip's length zeroed (xcp.degrade states the integer arithmetic and
+    ``degrade_reference`` restates it byte for byte; include/xcp.h the table).  params: an
+    ``xcp.degrade.DegradeParams`` (validated here, then packed and copied to the device) or its packed device
+    form ``params.to(device)``, int32 [B, 16], which the kernel clamps instead.  out: a contiguous uint8
+    tensor of frames' shape that shares no memory with it (default: a new one).  Stream-ordered, nothing read
+    back: a call can be captured in a graph and replayed after the device table was rewritten in place."""
+    from .degrade import DEG_COLS, DegradeParams
+    if not torch.is_tensor(frames) or frames.dim() != 5 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+        raise ValueError("clip_degrade: frames is a uint8 [B, T, H, W, 3] tensor")
+    B, T, H, W, _ = frames.shape
+    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+        raise ValueError("clip_degrade: lengths is an int32 [B] tensor")
+    if min(B, T, H, W) < 1 or H * W * 3 >= 2 ** 31:
+        raise ValueError("clip_degrade: frames is empty, or one frame has 2^31 bytes or more")
+    if isinstance(params, DegradeParams):
+        params.validate(B)
+        params = params.to(frames.device)
+    if not torch.is_tensor(params) or params.dtype != torch.int32 or tuple(params.shape) != (B, DEG_COLS) \
+            or not params.is_contiguous():
+        raise ValueError(f"clip_degrade: the device table is a contiguous int32 [B, {DEG_COLS}] tensor")
+    check_gpu(frames, lengths, params)
+    frames, lengths = frames.contiguous(), lengths.contiguous()
+    if out is None:
+        out = torch.empty_like(frames)
+    else:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.shape != frames.shape or not out.is_contiguous():
+            raise ValueError("clip_degrade: out is a contiguous uint8 tensor of frames' shape")
+        check_gpu(out)
+        n = frames.numel()
+        if out.data_ptr() < frames.data_ptr() + n and frames.data_ptr() < out.data_ptr() + n:
+            raise ValueError("clip_degrade: out must not overlap frames")
+    _lib.call("xcp_clip_degrade", _p(frames), _p(lengths), _p(params), _p(out), B, T, H, W, stream())
+    return out
+
+
 def mfcc(wav, lengths, plan, table=None, out_frames=None, channels=3, dtype=torch.float32):
     """Padded PCM waveforms -> MFCC frames in two kernels (csrc/mfcc.hip; xcp.audio states the arithmetic
     and restates it in fp64).  wav: fp32 or int16 [B, Nmax]; lengths: int32 [B]; plan: an
