@@ -344,13 +344,37 @@ def unit_dy(G, Y, coef):
 DW_FWD_SHAPES = [(2, 64, 17, 41),      # tile_geo: ntw 2, TW 21, WP 27, nth 2: 2 x 2 ragged tiles, ragged last segment
                  (8, 728, 19, 19),     # N % 8 == 0: frames dealt to the XCDs (fwd_item_id); last group 24 of 32 channels
                  (3, 728, 19, 19),     # the xcd_remap order
-                 (2, 72, 5, 9),        # narrowest frame of the tile kernel; last group 8 channels
+                 (2, 72, 5, 9),        # W = 9: the narrowest frame past dwframe.hip's W <= 8 gate (W = 3, 5, 6, 7 are
+                                       # not among its widths and reach the tile kernels too: below); last group 8 channels
                  (3, 1536, 10, 10),    # 128-B slices
-                 (3, 200, 7, 8), (5, 728, 3, 4), (2, 64, 1, 2)]   # dwframe.hip (fp32 windows: no bf16 staging)
+                 (3, 200, 7, 8), (5, 728, 3, 4), (2, 64, 1, 2),   # dwframe.hip (fp32 windows: no bf16 staging)
+                 # the small and odd frames of the 64^2, 75^2, 224^2 and 256^2 families
+                 (40, 728, 1, 1),      # dwframe W = 1 (a 1 x 1 exit): only the centre tap sees the frame
+                 (16, 1536, 2, 2),     # dwframe W = 2: the 64^2 exit flow, every pixel a corner
+                 (6, 728, 4, 4),       # dwframe W = 4: the 64^2 middle flow
+                 (3, 728, 5, 3),       # 75^2 exit: W = 3 is not a dwframe width -> tile kernel, one 5-pixel segment of 3
+                 (4, 1024, 3, 3),      # 75^2 exit, 128-B slices (2 C % 128 == 0): dw_fwd_kernel, 3 x 3
+                 (2, 64, 6, 7),        # W = 7, H = 6, 128-B slices with a single group of 64 channels
+                 (2, 72, 1, 9),        # H = 1 in the tile kernel: both halo rows are padding
+                 (3, 728, 7, 7),       # 224^2 exit flow: tile kernel, two segments 5 + 2
+                 (3, 256, 15, 15),     # 64^2 entry flow (256 channels: 17 x 17 > 256 halo pixels, so 64-B slices)
+                 (2, 128, 29, 29)]     # 64^2 entry flow: WP 32, three row tiles 10 + 10 + 9
 DW_BWD_SHAPES = [(2, 72, 9, 21),       # two column groups, 20 + 1
                  (2, 64, 64, 5),       # three row bands
                  (3, 728, 19, 19),
-                 (2, 128, 15, 15)]
+                 (2, 128, 15, 15),
+                 # the frames below 9 x 21: one row band and (up to 15 x 8) one 20-column group, most or all pixels
+                 # edge pixels; the skip forms see a 1 x 1, 2 x 2, 3 x 2, ... dskip
+                 (40, 728, 1, 1),      # H = 1: dY rows -1 and 1 are both padding, one live column of the 22 staged
+                 (16, 1536, 2, 2),     # 64^2 exit flow (1536 channels)
+                 (8, 1024, 2, 2),      # 64^2 exit flow (1024 channels)
+                 (6, 728, 4, 4),       # 64^2 middle flow
+                 (3, 728, 5, 3),       # 75^2 exit, non-square
+                 (4, 1024, 3, 3),      # 75^2 exit
+                 (3, 728, 7, 7),       # 224^2 exit flow
+                 (2, 128, 8, 8),       # 256^2 / 64^2: 8 x 8
+                 (2, 256, 15, 8),      # non-square, odd x even: dskip 8 x 4
+                 (1, 128, 29, 29)]     # 64^2 entry flow: two column groups 20 + 9, dskip 15 x 15
 # form, act
 DW_BWD_FORMS = [("plain", 0), ("plain", 1), ("plain", 2), ("res", 1), ("skip", 2), ("res+skip", 1), ("resbn", 2),
                 ("skip_pre", 2)]
@@ -365,7 +389,13 @@ GATHER1_SHAPES = [(3, 37, 37, 256, 728, 256, 2),     # 1083 rows: 9 M-tiles, the
                   (2, 10, 7, 8, 8, 8, 2),            # one 16-byte bf16 chunk per row
                   (1, 1, 1, 64, 64, 64, 2),          # M = 1
                   (2, 11, 8, 40, 24, 48, 3),         # stride 3: 4 x 3 of 11 x 8, pitch 48
-                  (2, 5, 9, 72, 136, 72, 1)]         # stride 1: bitwise the dense call
+                  (2, 5, 9, 72, 136, 72, 1),         # stride 1: bitwise the dense call
+                  # the skip convs of the 64^2 family (and 256^2's 8 -> 4) at the workload's channel counts
+                  (2, 29, 29, 64, 128, 64, 2),       # 29 -> 15: 450 rows, K = one 64-column stage
+                  (3, 15, 15, 128, 256, 128, 2),     # 15 -> 8: 192 rows, odd W: the last column is sampled
+                  (4, 8, 8, 256, 728, 256, 2),       # 8 -> 4: 64 rows (half an M-tile), even W
+                  (5, 4, 4, 728, 1024, 736, 2),      # 4 -> 2: 20 rows, K tail of 24, pitch 736
+                  (3, 2, 2, 728, 1024, 736, 2)]      # 2 -> 1: 3 rows, one sampled pixel of four per frame
 # gather modes 2 / 3 (im2col of the 3x3 valid conv and its transpose): N, H, W, gC (K = 9 gC)
 IM2COL_SHAPES = [(2, 21, 19, 32),     # K = 288 = 4 * 64 + 32: a half-filled last K-stage (bf16)
                  (1, 3, 3, 32),       # one output pixel (mode 2); every pixel sees exactly one tap (mode 3)
@@ -483,6 +513,68 @@ def maxpool3s2_bwd_ref(dout, amax, H, W):
         g[:, ky:ky + 2 * OH:2, kx:kx + 2 * OW:2] += sel
         ab[:, ky:ky + 2 * OH:2, kx:kx + 2 * OW:2] += sel.abs()
     return g[:, 1:H + 1, 1:W + 1].contiguous(), ab[:, 1:H + 1, 1:W + 1].contiguous()
+
+
+def tail_plain_ref(y, s1, t1, skip, s2=None, t2=None):
+    """The un-pooled block tail (tail_fwd_kernel, pool = 0): out = fmaf(y, s1, t1) + (skip, or fmaf(skip, s2, t2)):
+    two exactly restated fp32 values and one fp32 add, n = 2 -> (ref64, abs_terms)"""
+    z = fma32(y, s1, t1).double()
+    sk = skip.double() if s2 is None else fma32(skip, s2, t2).double()
+    return z + sk, z.abs() + sk.abs()
+
+
+# N, C, H, W of the pooled tail, max-pool backward and its fused BN reduce.  N H W <= ~1100: the fp32-sum bound of
+# the reduce is sharp only there (assert_f32_sum).  tail_pool_quad_kernel works per 2 x 2 quad of outputs, so an odd
+# OH or OW is its ragged quad (clamped skip loads, skipped stores); maxpool_bwd_red_kernel's advance() steps
+# SPB = 256 / CVB quads (chanred_geo) at a time, which is several whole frames where OH OW < SPB.
+POOL_SHAPES = [(2, 128, 19, 20), (2, 128, 20, 19),    # -> 10 x 10 from an odd and an even extent: windows over both edges
+               (1, 128, 37, 21),      # 299^2's 37 -> 19, by 11: odd x odd outputs, both quad edges ragged
+               (1, 128, 29, 29),      # 64^2: 29 -> 15
+               (4, 256, 15, 15),      # 64^2: 15 -> 8, 256 channels (SPB 8)
+               (16, 736, 8, 8),       # 8 -> 4 at the pitch of 728: nch 2, CVB 46, SPB 5, 26 idle threads per workgroup
+               (60, 1024, 4, 4),      # 4 -> 2: SPB 4 = one frame of quads per step
+               (200, 1024, 2, 2),     # 2 -> 1: a step of advance() is four frames
+               (300, 64, 1, 1),       # 1 -> 1: one pixel, tap 4 only; SPB 32
+               (3, 728, 5, 3),        # 75^2 exit: -> 3 x 2, non-square
+               (2, 8, 7, 9),          # C = 8: one channel vector, SPB 256 > the 40 quads
+               (2, 256, 14, 14)]      # 224^2: 14 -> 7, an even input with an odd output
+TAIL_PLAIN_SHAPES = [(3, 736, 19, 19),   # the middle flow's residual add at the pitch of 728
+                     (2, 1024, 2, 3),    # 12 pixels, non-square (an exit-flow frame)
+                     (5, 64, 1, 1)]      # 40 threads
+AVGPOOL_SHAPES = [(3, 264, 100), (2, 2048, 49),       # N, C, HW
+                  (3, 2048, 4), (2, 2048, 1), (5, 2048, 9), (2, 8, 6)]   # 64^2, a 1 x 1 exit, 75^2; one channel vector
+
+
+def pool_inputs(N, C, H, W, pool=True, salt=0):
+    """What a block-tail / max-pool case reads, generated on the CPU: y [N,H,W,C], the skip ys and the pooled
+    gradient d at the output size, the two BN affines"""
+    OH, OW = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if pool else (H, W)
+    g = torch.Generator().manual_seed(H * 100 + W + salt)
+    d = {"y": torch.randn(N, H, W, C, generator=g).bfloat16(), "ys": torch.randn(N, OH, OW, C, generator=g).bfloat16()}
+    d["s1"], d["s2"] = (torch.rand(C, generator=g) + 0.5 for _ in range(2))
+    d["t1"], d["t2"] = (torch.randn(C, generator=g) for _ in range(2))
+    d["d"] = torch.randn(N, OH, OW, C, generator=g).bfloat16()
+    d["OH"], d["OW"] = OH, OW
+    return d
+
+
+def batch_stats(y):
+    """the batch's own mean / invstd of y [N,H,W,C] (so the dz zhat sums cancel) as fp32"""
+    yd = y.double()
+    return {"mean": yd.mean((0, 1, 2)).float(), "invstd": (1 / (yd.var((0, 1, 2), unbiased=False) + 1e-5).sqrt()).float()}
+
+
+def chanred_geo(rows, C, cpt=8, target=1024):
+    """make_chanred (csrc/bn.hip) restated: nch channel chunks of CVB vectors, SPB row slots per workgroup, P row
+    chunks of rpc rows (the partial rows the reduce writes)"""
+    cdiv = lambda a, b: -(-a // b)
+    CV = C // cpt
+    nch = cdiv(CV, 64)
+    CVB = cdiv(CV, nch)
+    SPB = 256 // CVB
+    P = max(1, min(max(1, target // nch), cdiv(rows, 4 * SPB)))
+    rpc = cdiv(rows, P)
+    return {"nch": nch, "CVB": CVB, "SPB": SPB, "rpc": rpc, "P": cdiv(rows, rpc)}
 
 
 def conv3x3_valid_ref(a, w, flip=None):

@@ -8,6 +8,10 @@ share >= 0.99.  The nine-slice pool references are checked against torch's own p
 
 Sharp: planted defects that the norm measure of test_gpu_kernels.py lets through make it raise.
 
+The block tails and pools (E.POOL_SHAPES, E.TAIL_PLAIN_SHAPES: the small and odd frames of the 64^2, 75^2, 224^2
+and 256^2 families) get the same two halves after the pool references: fp32 emulations of the pooled and the
+un-pooled tail, the max-pool backward and the fused BN sums, and four defects of those edges, one thread's share each.
+
 The second half does the same for the stem convolutions and the BatchNorm statistics chain
 (test_gpu_elementwise_stem_bn.py): the split-bf16 allowance of the conv1 row kernels is shown to be enough by
 an emulation that forms hi / lo with .bfloat16() and adds the product groups in fp32; the finalize bounds by
@@ -246,7 +250,7 @@ def test_sharp_wgrad_pixel_dropped():
 
 
 # ------------------------------------------------------------------ pools
-@pytest.mark.parametrize("H,W", [(19, 20), (20, 19), (1, 2)])
+@pytest.mark.parametrize("H,W", sorted({(1, 2)} | {s[2:] for s in E.POOL_SHAPES}))
 def test_maxpool_refs_against_torch(H, W):
     """the nine-slice max pool and its scatter backward equal torch's (fp64, no ties in random data)"""
     g = torch.Generator().manual_seed(H * W)
@@ -266,6 +270,175 @@ def test_maxpool_first_max_rule():
     z[0, 1, 1, 0] = z[0, 2, 2, 0] = 5.0      # window (1, 1) holds both: taps 0 and 4, the first wins
     m, am = E.maxpool3s2_ref(z)
     assert am[0, :, :, 0].tolist() == [[8, 6], [2, 0]] and (m == 5).all()
+
+
+# ------------------------------------------------------------------ block tails and pools at small and odd frames
+def emu_tail(d, pool, bn_skip):
+    """the block tail in fp32: fmaf as fma32, the first-max pool of the exact fp32 values, one fp32 add, a bf16
+    store -> (out bf16, argmax taps or None)"""
+    z = E.fma32(d["y"], d["s1"], d["t1"])
+    am = None
+    if pool:
+        z, am = E.maxpool3s2_ref(z)
+    sk = E.fma32(d["ys"], d["s2"], d["t2"]) if bn_skip else d["ys"].float()
+    return (z + sk).bfloat16(), am
+
+
+def emu_maxpool_bwd(dout, amax, H, W):
+    """maxpool3s2_bwd_ref's scatter with fp32 additions (window order), stored bf16"""
+    N, OH, OW, C = dout.shape
+    g = torch.zeros(N, H + 2, W + 2, C)
+    d = dout.float()
+    for t in range(9):
+        ky, kx = divmod(t, 3)
+        g[:, ky:ky + 2 * OH:2, kx:kx + 2 * OW:2] += d * (amax == t)
+    return g[:, 1:H + 1, 1:W + 1].bfloat16()
+
+
+def emu_bn_sums(dz, y, st, order=0):
+    """(sum dz, sum dz zhat) over the stored dz in fp32, zhat by the kernel's two fp32 operations"""
+    dzf = dz.float()
+    return torch.stack([psum(dzf, order), psum(dzf * ((y.float() - st["mean"]) * st["invstd"]), order)])
+
+
+def pool_refs(d, bn_skip=True):
+    """(ref64, abs_terms, argmax) of the pooled tail's out"""
+    H, W = d["y"].shape[1:3]
+    m, am = E.maxpool3s2_ref(E.fma32(d["y"], d["s1"], d["t1"]))
+    sk = (E.fma32(d["ys"], d["s2"], d["t2"]) if bn_skip else d["ys"]).double()
+    return m.double() + sk, m.double().abs() + sk.abs(), am
+
+
+def test_pool_shapes_reach_what_their_comments_say():
+    """the launch geometry restated from make_chanred (the GPU file asserts the library's P equals it)"""
+    geo = {s: E.chanred_geo(s[0] * ((s[2] - 1) // 2 + 1) * ((s[3] - 1) // 2 + 1), s[1]) for s in E.POOL_SHAPES}
+    g = geo[(16, 736, 8, 8)]
+    assert (g["nch"], g["CVB"], g["SPB"]) == (2, 46, 5) and 256 - g["CVB"] * g["SPB"] == 26
+    assert geo[(60, 1024, 4, 4)]["SPB"] == 4 and geo[(200, 1024, 2, 2)]["SPB"] == 4
+    assert geo[(2, 8, 7, 9)]["SPB"] == 256 and geo[(300, 64, 1, 1)]["SPB"] == 32
+    assert (geo[(200, 1024, 2, 2)]["rpc"], geo[(200, 1024, 2, 2)]["P"]) == (16, 13)     # 12 full chunks and one of 8
+    odd = [s for s in E.POOL_SHAPES if ((s[2] - 1) // 2 + 1) % 2 or ((s[3] - 1) // 2 + 1) % 2]
+    assert len(odd) >= 7 and (2, 256, 14, 14) in odd and all(s[0] * s[2] * s[3] <= 1100 for s in E.POOL_SHAPES)
+
+
+@pytest.mark.parametrize("bn_skip", [True, False], ids=["bn_skip", "identity_skip"])
+@pytest.mark.parametrize("shape", E.POOL_SHAPES, ids=str)
+def test_sound_tail_pool(shape, bn_skip):
+    """the fp32 emulation of the pooled tail, the max-pool backward and the fused BN sums sits inside the bounds
+    the GPU files hold the kernels to, on their data"""
+    N, C, H, W = shape
+    d = E.pool_inputs(N, C, H, W)
+    ref, ab, am = pool_refs(d, bn_skip)
+    out, am_e = emu_tail(d, True, bn_skip)
+    st = E.assert_bf16_stored(out, ref, ab, 2)
+    assert st["nearest"] >= 0.99 and torch.equal(am_e, am)
+    zref, zab = E.maxpool3s2_bwd_ref(d["d"], am, H, W)
+    dz = emu_maxpool_bwd(d["d"], am, H, W)
+    assert E.assert_bf16_stored(dz, zref, zab, 4)["nearest"] >= 0.99
+    stats = E.batch_stats(d["y"])
+    sref, sab = E.bn_sums_ref(dz, d["y"], stats["mean"], stats["invstd"])
+    for order in (0, 1):
+        E.assert_f32_sum(emu_bn_sums(dz, d["y"], stats, order), sref, sab, N * H * W)
+
+
+@pytest.mark.parametrize("bn_skip", [True, False], ids=["bn_skip", "identity_skip"])
+@pytest.mark.parametrize("shape", E.TAIL_PLAIN_SHAPES, ids=str)
+def test_sound_tail_plain(shape, bn_skip):
+    N, C, H, W = shape
+    d = E.pool_inputs(N, C, H, W, pool=False)
+    ref, ab = E.tail_plain_ref(d["y"], d["s1"], d["t1"], d["ys"], *((d["s2"], d["t2"]) if bn_skip else ()))
+    st = E.assert_bf16_stored(emu_tail(d, False, bn_skip)[0], ref, ab, 2)
+    assert st["nearest"] >= 0.99 and st["excluded"] == 0
+
+
+# Sharp at these edges.  Each defect is planted at the grain of ONE THREAD of the kernel it models (a quad of pixels
+# and 8 channels; a lane's channel pair in the depthwise backward): the tensors here are small (16 000 to 750 000
+# elements), and a defect across all channels of a column or a frame is norm-wise visible in them -- the last
+# output column of (1, 128, 37, 21) shifted in every row and channel is rel_err 0.060, one frame's lost window row
+# at (60, 1024, 4, 4) 0.049, one frame left out of every channel's sums at (200, 1024, 2, 2) 0.063.  One thread's
+# share passes rel_err < 1e-2 and is the harder catch for the element-wise measure.
+def test_sharp_tail_pool_last_column_from_the_clamped_window():
+    """(1, 128, 37, 21) -> 19 x 11: the ragged quad column.  The last output column of the last quad row takes its
+    window one pixel to the left (columns 18 .. 20 instead of 19 .. 21, the clamped start), 8 channels."""
+    N, C, H, W = 1, 128, 37, 21
+    d = E.pool_inputs(N, C, H, W)
+    ref, ab, _ = pool_refs(d)
+    out, _ = emu_tail(d, True, True)
+    E.assert_bf16_stored(out, ref, ab, 2)
+    OH, OW = d["OH"], d["OW"]
+    assert OH % 2 == 1 and OW % 2 == 1
+    z = E.fma32(d["y"], d["s1"], d["t1"])
+    p = F.pad(z, (0, 0, 1, 1, 1, 1), value=float("-inf"))
+    ow, c = OW - 1, slice(40, 48)
+    left = torch.stack([p[:, ky:ky + 2 * OH:2, 2 * ow + kx - 1] for ky in range(3) for kx in range(3)]).max(0)[0]
+    sk = E.fma32(d["ys"], d["s2"], d["t2"])
+    oh = OH - 1                                   # the corner quad holds this one valid output
+    bad = out.clone()
+    bad[:, oh, ow, c] = (left[:, oh, c] + sk[:, oh, ow, c]).bfloat16()
+    assert 1 <= (bad != out).sum() <= 8
+    caught(bad, ref, ab, 2)
+
+
+def test_sharp_maxpool_bwd_window_below_taken_as_absent():
+    """(60, 1024, 4, 4) -> 2 x 2: in one frame, quad (0, 0) treats window (a + 1, b) as absent, as the last quad
+    row rightly does: pixels (1, 0) and (1, 1) lose what that window sends them (taps 1 and 2), 8 channels."""
+    N, C, H, W = 60, 1024, 4, 4
+    d = E.pool_inputs(N, C, H, W)
+    _, _, am = pool_refs(d)
+    ref, ab = E.maxpool3s2_bwd_ref(d["d"], am, H, W)
+    E.assert_bf16_stored(emu_maxpool_bwd(d["d"], am, H, W), ref, ab, 4)
+    n, c = 17, slice(40, 48)
+    absent = am.clone()
+    w = absent[n, 1, 0, c]                         # window (a + 1, b) = (1, 0) of quad (0, 0)
+    w[(w == 1) | (w == 2)] = 0xFF                   # never matches a tap
+    bad = emu_maxpool_bwd(d["d"], absent, H, W)
+    lost = (bad != emu_maxpool_bwd(d["d"], am, H, W))
+    assert 1 <= lost.sum() <= 8 and lost[n, 1, :2, c].sum() == lost.sum()
+    caught(bad, ref, ab, 4)
+
+
+def test_sharp_dw_bwd_corner_tap_at_two_by_two():
+    """(16, 1536, 2, 2), plain, act 2: the bottom-right pixel's dX of one frame without the tap from its upper-left
+    neighbour (dY[0, 0] w[8]: one of its four live taps), one lane's channel pair"""
+    N, C, H, W = 16, 1536, 2, 2
+    d = E.dw_inputs(N, C, H, W)
+    r = E.dw_bwd_ref(d["dy"], d["x"], d["wt"], 2, d["scale"], d["shift"])
+    dx, _, _ = emu_dw_bwd(d, 2, "plain", 0)
+    E.assert_bf16_stored(dx, r["dx"], r["dx_abs"], 11, exclude=r["dx_excl"])
+    n = 9
+    _, mask = emu_act(d["x"], 2, d["scale"], d["shift"], False)
+    live = [c for c in range(0, C, 2) if mask[n, 1, 1, c] and mask[n, 1, 1, c + 1]][3]      # both channels pass the ReLU
+    c = slice(live, live + 2)
+    s = emu_taps(d["dy"].float(), d["wt"], True, 0)[n, 1, 1, c]
+    bad = dx.clone()
+    bad[n, 1, 1, c] = (s - d["dy"][n, 0, 0, c].float() * d["wt"][8, c]).bfloat16()
+    assert (bad != dx).sum() == 2
+    assert rel_err(bad.float(), r["dx"]) < 1e-2
+    with pytest.raises(AssertionError, match="outside the bf16-neighbour bound"):
+        E.assert_bf16_stored(bad, r["dx"], r["dx_abs"], 11, exclude=r["dx_excl"])
+
+
+def test_sharp_pool_bn_sums_skip_a_frame_after_a_chunk_boundary():
+    """(200, 1024, 2, 2) -> 1 x 1: a quad is a frame, SPB = 4, 13 chunks of 16.  One thread's 8 channels leave out the
+    first frame of chunk 1 (an advance() that overshoots by one frame): the sums stay within rel_err < 1e-2 and
+    leave the fp32 bound of their 800 terms."""
+    N, C, H, W = 200, 1024, 2, 2
+    d = E.pool_inputs(N, C, H, W, salt=1)
+    _, _, am = pool_refs(d)
+    dz = emu_maxpool_bwd(d["d"], am, H, W)
+    st = E.batch_stats(d["y"])
+    ref, ab = E.bn_sums_ref(dz, d["y"], st["mean"], st["invstd"])
+    good = emu_bn_sums(dz, d["y"], st)
+    E.assert_f32_sum(good, ref, ab, N * H * W)
+    f = E.chanred_geo(N, C)["rpc"]
+    assert f == 16
+    keep = torch.arange(N) != f
+    bad = good.clone()
+    bad[:, 40:48] = emu_bn_sums(dz[keep], d["y"][keep], st)[:, 40:48]
+    assert (bad != good).any(0).sum() == 8
+    assert rel_err(bad, ref) < 1e-2
+    with pytest.raises(AssertionError, match="outside the fp32 bound"):
+        E.assert_f32_sum(bad, ref, ab, N * H * W)
 
 
 # ================================================================== stem convs and BN statistics

@@ -2,13 +2,16 @@
 an fp64 restatement (tests/elementwise.py: every bound is derived there, none is fitted):
 dw_fwd (tile, w2, 128-B-slice and tiny-frame kernels), dw_bwd (every launch form), the NT GEMMs
 (128x128, 256x256, persistent) with their BN partial sums, the TN GEMMs and the fused unit backward;
-then, with the same helper, the pooled block tail and max-pool backward on non-square frames, the
-average pool, bn_act / bn_apply_coef and the stem conv3x3 forward.
+then, with the same helper, the pooled block tail (BN'd and identity skip) and max-pool backward on non-square,
+odd and tiny frames (E.POOL_SHAPES: down to 1 x 1, 8 to 1024 channels), the un-pooled block tail, the average
+pool (HW from 100 down to 1), bn_act / bn_apply_coef and the stem conv3x3 forward.  The depthwise lists hold the
+frames of the 299^2 family and the small and odd ones of the 64^2, 75^2, 224^2 and 256^2 families.
 The shapes are the smallest ragged ones that reach each path; the inputs are generated on the CPU,
 so test_elementwise_cpu.py has judged the measure on the same data.  Outputs start as NaN.
 
 Every case prints one "ELEMENTWISE" line per output: the worst d/lim, and for bf16 outputs the
-share rounded to nearest and the share excluded (profiles/elementwise_fp64_bounds.txt)."""
+share rounded to nearest and the share excluded (profiles/elementwise_fp64_bounds.txt,
+profiles/elementwise_small_frames.txt)."""
 import pytest
 import torch
 
@@ -145,39 +148,53 @@ def test_unit_bwd(ops, gpu, shape):
                                           tag=case + " dW accumulate"))
 
 
-@pytest.mark.parametrize("H,W", [(19, 20), (20, 19)])
-def test_tail_maxpool(ops, gpu, H, W):
-    """Block tail out = maxpool3x3s2(fmaf(y, s1, t1)) + fmaf(skip, s2, t2) (two fp32 values, one fp32 add: n = 2)
-    on non-square frames whose windows hang over both edges, the argmax bytes against the first-max rule, and
-    maxpool_bwd (<= 4 windows per pixel) from those bytes."""
-    N, C = 2, 128
-    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    g = torch.Generator().manual_seed(H * 100 + W)
-    y = torch.randn(N, H, W, C, generator=g).bfloat16().to(gpu)
-    ys = torch.randn(N, OH, OW, C, generator=g).bfloat16().to(gpu)
-    s1, s2 = ((torch.rand(C, generator=g) + 0.5).to(gpu) for _ in range(2))
-    t1, t2 = (torch.randn(C, generator=g).to(gpu) for _ in range(2))
-    d = torch.randn(N, OH, OW, C, generator=g).bfloat16().to(gpu)
+@pytest.mark.parametrize("bn_skip", [True, False], ids=["bn_skip", "identity_skip"])
+@pytest.mark.parametrize("shape", E.POOL_SHAPES, ids=str)
+def test_tail_maxpool(ops, gpu, shape, bn_skip):
+    """Block tail out = maxpool3x3s2(fmaf(y, s1, t1)) + fmaf(skip, s2, t2) (two fp32 values, one fp32 add: n = 2;
+    identity_skip: s2 = t2 = None, the skip added as it is) on frames whose windows hang over both edges, down to
+    1 x 1, with odd OH / OW (the ragged output quad) and 8 to 1024 channels; the argmax bytes against the
+    first-max rule, and maxpool_bwd (<= 4 windows per pixel) from those bytes."""
+    N, C, H, W = shape
+    d = to(E.pool_inputs(N, C, H, W), gpu)
+    OH, OW = d["OH"], d["OW"]
+    s2, t2 = (d["s2"], d["t2"]) if bn_skip else (None, None)
     out = torch.full((N, OH, OW, C), NAN, device=gpu, dtype=torch.bfloat16)
     amax = torch.full((N, OH, OW, C), 0xEE, device=gpu, dtype=torch.uint8)
-    ops.tail_fwd(y, s1, t1, True, ys, s2, t2, out, amax, N, H, W, C)
+    ops.tail_fwd(d["y"], d["s1"], d["t1"], True, d["ys"], s2, t2, out, amax, N, H, W, C)
     dz = torch.full((N, H, W, C), NAN, device=gpu, dtype=torch.bfloat16)
-    ops.maxpool_bwd(d, amax, dz, N, H, W, C)
+    ops.maxpool_bwd(d["d"], amax, dz, N, H, W, C)
     torch.cuda.synchronize()
-    m, am = E.maxpool3s2_ref(E.fma32(y, s1, t1))
-    sk = E.fma32(ys, s2, t2).double()
-    case = f"tail_fwd (2, 128, {H}, {W})"
+    m, am = E.maxpool3s2_ref(E.fma32(d["y"], d["s1"], d["t1"]))
+    sk = (E.fma32(d["ys"], s2, t2) if bn_skip else d["ys"]).double()
+    case = f"tail_fwd {shape}{'' if bn_skip else ' identity_skip'}"
     record(case, "out", E.assert_bf16_stored(out, m.double() + sk, m.double().abs() + sk.abs(), 2, tag=case))
     assert torch.equal(amax, am), f"{case}: {(amax != am).sum().item()} argmax bytes differ from the first-max rule"
-    ref, ab = E.maxpool3s2_bwd_ref(d, am, H, W)
-    case = f"maxpool_bwd (2, 128, {H}, {W})"
+    ref, ab = E.maxpool3s2_bwd_ref(d["d"], am, H, W)
+    case = f"maxpool_bwd {shape}{'' if bn_skip else ' identity_skip'}"
     record(case, "dz", E.assert_bf16_stored(dz, ref, ab, 4, tag=case))
 
 
-@pytest.mark.parametrize("N,C,HW", [(3, 264, 100), (2, 2048, 49)])
+@pytest.mark.parametrize("bn_skip", [False, True], ids=["identity_skip", "bn_skip"])
+@pytest.mark.parametrize("shape", E.TAIL_PLAIN_SHAPES, ids=str)
+def test_tail_plain(ops, gpu, shape, bn_skip):
+    """The un-pooled block tail (tail_fwd_kernel, pool = 0): out = fmaf(y, s1, t1) + skip -- the residual add of the
+    middle-flow blocks -- or + fmaf(skip, s2, t2); n = 2.  No argmax buffer is passed."""
+    N, C, H, W = shape
+    d = to(E.pool_inputs(N, C, H, W, pool=False), gpu)
+    s2, t2 = (d["s2"], d["t2"]) if bn_skip else (None, None)
+    out = torch.full((N, H, W, C), NAN, device=gpu, dtype=torch.bfloat16)
+    ops.tail_fwd(d["y"], d["s1"], d["t1"], False, d["ys"], s2, t2, out, None, N, H, W, C)
+    torch.cuda.synchronize()
+    ref, ab = E.tail_plain_ref(d["y"], d["s1"], d["t1"], d["ys"], s2, t2)
+    case = f"tail_plain {shape} {'bn_skip' if bn_skip else 'identity_skip'}"
+    record(case, "out", E.assert_bf16_stored(out, ref, ab, 2, tag=case))
+
+
+@pytest.mark.parametrize("N,C,HW", E.AVGPOOL_SHAPES)
 def test_avgpool(ops, gpu, N, C, HW):
-    """F = (sum_p max(fmaf(y, s, t), 0)) / HW in fp32 (HW terms); dz = bf16(mask * (dF * fp32(1 / HW))) (one
-    exact-in-fp64 product), the mask excluded where fmaf's sign is within rounding of undecided."""
+    """F = (sum_p max(fmaf(y, s, t), 0)) / HW in fp32 (HW terms, down to HW = 1); dz = bf16(mask * (dF * fp32(1 / HW)))
+    (one exact-in-fp64 product), the mask excluded where fmaf's sign is within rounding of undecided."""
     g = torch.Generator().manual_seed(N + C + HW)
     y = torch.randn(N, HW, C, generator=g).bfloat16().to(gpu)
     s = (torch.rand(C, generator=g) + 0.5).to(gpu)

@@ -4,7 +4,8 @@ materialised by plain slicing (gather_rows, proven against torch's convolutions 
 and its `abs_terms` come from gemm_nt_ref / gemm_tn_ref, every bound is derived from the number of terms.
 
 gemm_nt, mode 1 (the stride-2 skip conv): bf16 and fp32, with and without the BN partial sums, a K tail, a
-pitch wider than K, M = 1, strides 1 to 3.  Every element of A the gather must not read is NaN; A, like
+pitch wider than K, M = 1, strides 1 to 3, and the skip convs of the small frames (29 -> 15 down to 2 -> 1, 450 to 3
+rows) at the workload's channel counts.  Every element of A the gather must not read is NaN; A, like
 every gathered operand here, sits between NaN margins; C and the partial sums start as NaN.
 gemm_nt, modes 2 / 3 (conv2 forward and input gradient): one output pixel, one visible tap per pixel, M-tiles
 that span frames, five frames in one tile, gC 8 / 32 / 64.
@@ -14,7 +15,8 @@ rows; ops.weight_grad end to end, plain and accumulating.
 The gather geometry guard of xcp_gemm_nt / xcp_gemm_tn: inconsistent calls are rejected before any launch.
 
 The inputs are generated on the CPU (test_elementwise_cpu.py has judged the measure on the same data).
-Every case prints one "ELEMENTWISE" line per output (profiles/elementwise_gather_gemm.txt)."""
+Every case prints one "ELEMENTWISE" line per output (profiles/elementwise_gather_gemm.txt,
+profiles/elementwise_small_frames.txt)."""
 import pytest
 import torch
 

@@ -2,7 +2,8 @@
 element by element against the fp64 restatements of tests/elementwise.py: conv1 forward (row, tile and
 per-pixel kernels), conv1_fwd_stats, the conv1 weight gradient in its three forms (plain, accumulate, BN1's
 backward apply fused), the conv2 input gradient and its weight gradient in the three XCP_CONV3_WGRAD forms,
-the channel reductions (row_stats, bn_bwd_reduce without and with the ReLU mask, maxpool_bwd_bnred), the
+the channel reductions (row_stats, bn_bwd_reduce without and with the ReLU mask, maxpool_bwd_bnred at every
+E.POOL_SHAPES frame, its dz judged here too), the
 finalize kernels on partial rows the test writes (every R edge, padded pitch, a dead, a constant and a
 far-from-zero channel), bn_act_strided and relu_bwd.
 
@@ -10,7 +11,8 @@ The inputs are generated on the CPU (test_elementwise_cpu.py has judged every bo
 outputs start as NaN and are judged on the CPU by the same reference code.  Shapes are the smallest that
 reach each path; where a launcher's arithmetic decides the path, elementwise.conv1_path restates it.
 
-Every case prints one "ELEMENTWISE" line per output (profiles/elementwise_stem_bn.txt)."""
+Every case prints one "ELEMENTWISE" line per output (profiles/elementwise_stem_bn.txt,
+profiles/elementwise_small_frames.txt)."""
 import pytest
 import torch
 
@@ -199,21 +201,19 @@ def test_chan_sums(ops, gpu, shape, dt, mode):
     record(case, "sums", E.assert_f32_sum(part.view(R, 2, C).double().sum(0).cpu(), ref, ab, rows, extra=extra, tag=case))
 
 
-@pytest.mark.parametrize("H,W", [(19, 20), (20, 19)])
-def test_maxpool_bwd_bnred(ops, gpu, H, W):
-    """dz bitwise maxpool_bwd's; the partial sums against the stored dz and y (n = N H W = 760)"""
-    N, C = 2, 128
-    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    g = torch.Generator().manual_seed(H * 100 + W + 1)
-    y = torch.randn(N, H, W, C, generator=g).bfloat16()
-    ys = torch.randn(N, OH, OW, C, generator=g).bfloat16().to(gpu)
-    s1, s2 = ((torch.rand(C, generator=g) + 0.5).to(gpu) for _ in range(2))
-    t1, t2 = (torch.randn(C, generator=g).to(gpu) for _ in range(2))
-    dOut = torch.randn(N, OH, OW, C, generator=g).bfloat16().to(gpu)
-    yd = y.double()
-    mean = yd.mean((0, 1, 2))
-    st = {"mean": mean.float(), "invstd": (1 / (yd.var((0, 1, 2), unbiased=False) + 1e-5).sqrt()).float()}
-    yg = y.to(gpu)
+@pytest.mark.parametrize("shape", E.POOL_SHAPES, ids=str)
+def test_maxpool_bwd_bnred(ops, gpu, shape):
+    """dz bitwise maxpool_bwd's, and that dz against the fp64 scatter of the pooled gradient (<= 4 windows per pixel);
+    the partial sums against the stored dz and y (n = N H W <= 1083).  maxpool_bwd_red_kernel walks SPB quads at a
+    time, several whole frames at the 4 x 4, 2 x 2 and 1 x 1 cases; R is make_chanred's P as E.chanred_geo restates
+    it."""
+    N, C, H, W = shape
+    d = E.pool_inputs(N, C, H, W, salt=1)
+    OH, OW = d["OH"], d["OW"]
+    y = d["y"]
+    st = E.batch_stats(y)
+    yg, ys, dOut = y.to(gpu), d["ys"].to(gpu), d["d"].to(gpu)
+    s1, s2, t1, t2 = (d[k].to(gpu) for k in ("s1", "s2", "t1", "t2"))
     out = nan((N, OH, OW, C), gpu, BF)
     amax = torch.full((N, OH, OW, C), 0xEE, device=gpu, dtype=torch.uint8)
     ops.tail_fwd(yg, s1, t1, True, ys, s2, t2, out, amax, N, H, W, C)
@@ -221,9 +221,14 @@ def test_maxpool_bwd_bnred(ops, gpu, H, W):
     ops.maxpool_bwd(dOut, amax, dz0, N, H, W, C)
     part, R = ops.maxpool_bwd_bnred(dOut, amax, dz, yg, {k: v.to(gpu) for k, v in st.items()}, N, H, W, C)
     torch.cuda.synchronize()
+    assert R == E.chanred_geo(N * OH * OW, C)["P"]
     assert torch.equal(dz, dz0)
+    _, am = E.maxpool3s2_ref(E.fma32(y, d["s1"], d["t1"]))
+    assert torch.equal(amax.cpu(), am)
+    zref, zab = E.maxpool3s2_bwd_ref(d["d"], am, H, W)
+    case = f"maxpool_bwd_bnred {shape} R{R}"
+    record(case, "dz", E.assert_bf16_stored(dz0.cpu(), zref, zab, 4, tag=case + " dz"))
     ref, ab = E.bn_sums_ref(dz.cpu(), y, st["mean"], st["invstd"])
-    case = f"maxpool_bwd_bnred (2, 128, {H}, {W}) R{R}"
     record(case, "sums", E.assert_f32_sum(part.view(R, 2, C).double().sum(0).cpu(), ref, ab, N * H * W, tag=case))
 
 
